@@ -12,6 +12,11 @@ on the data path (weak scaling; the only collectives are the timing barrier and 
 
 Launch: python bench.py [--gpus N --steps K --warmup W]; for N > 1 under
 python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
+
+A plain run does what `value` needs and no more: set-up, warm-up, the K timed steps, the round-trip
+check of the last step, the result line.  --full adds every side measurement to that line (per-kernel
+times and rooflines, package power, the host-resident and long-record legs, the CPU baselines);
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -59,9 +64,18 @@ def parse():
                     help="records per GPU (default 65 536; --c5: 524 288, BASELINE config 5)")
     ap.add_argument("--record-bytes", type=int, default=4096)
     ap.add_argument("--lanes", type=int, default=0, help="force lanes per record (0 = scheduler)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need and add it to the result "
+                         "line: per-kernel times with the HBM / VALU rooflines, package power, the "
+                         "host-resident legs, the long-record leg, the frame queues and the CPU "
+                         "baselines (each has its own --no-... switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (ciphertext, tags, "
+                         "opened plaintext, verdicts: the caller's output buffers) as DIR/<name>.npy, "
+                         "float32; buffers over 3 Mi bytes as a fixed seeded sample of their bytes")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--no-power", action="store_true",
-                    help="skip the rocm-smi package power / sclk sample after the timed region")
+                    help="--full: skip the rocm-smi package power / sclk sample after the timed region")
     ap.add_argument("--cpu-seconds", type=float, default=10.0,
                     help="approximate wall budget of the CPU baseline sample")
     ap.add_argument("--e2e", action="store_true",
@@ -79,14 +93,14 @@ def parse():
     ap.add_argument("--no-pin", action="store_true",
                     help="do not pin this rank (and its host children) to its GPU's NUMA node CPUs")
     ap.add_argument("--no-long", action="store_true",
-                    help="skip the long-record side leg (1 x 32 MiB, 8 x 1 MiB)")
+                    help="--full: skip the long-record side leg (1 x 32 MiB, 8 x 1 MiB)")
     ap.add_argument("--long-only", action="store_true",
                     help="print only the long-record side leg (device-resident) and exit")
     ap.add_argument("--no-e2e", action="store_true",
                     help="host-resident keys: only the C5 share (no C2 e2e child) -- the one-GPU N = 8 "
                          "rehearsal, where 8 ranks + 8 children already use the box's 16 GPU process slots")
     ap.add_argument("--no-host", action="store_true",
-                    help="default line: skip the host-resident extra keys (C2 e2e, C5 per-GPU share)")
+                    help="--full: skip the host-resident extra keys (C2 e2e, C5 per-GPU share)")
     ap.add_argument("--c5-chunk-mib", type=int, default=0,
                     help="host pipeline chunk size for --c5 (one lane hashes a whole record, so "
                          "mixed batches with HMAC want big chunks)")
@@ -123,6 +137,10 @@ def parse():
                          "probe); wire = session wire frames seal+open (SURVEY 8f row 1, messages "
                          "of --record-bytes); store = chunk store+fetch pipeline (8f row 2)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and (a.mode == "pow" or a.c5 or a.c5_device or a.e2e or a.long_only):
+        ap.error("--dump-outputs goes with the device-resident seal/open modes (aead, xor, wire, store)")
     a.records_given = a.records is not None
     if a.records is None:
         a.records = 65536
@@ -969,7 +987,7 @@ def pow_bench(args) -> dict:
             "compressions_per_candidate": 1,
             "sha_rounds_per_candidate": 64 - plen % 64 // 4,
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             import ctypes as C
 
             threads = host_threads()
@@ -1122,6 +1140,26 @@ def long_records_leg(dev, reps: int = 20) -> dict:
     return res
 
 
+DUMP_SAMPLE = 3 << 20  # elements kept of an output buffer larger than this
+
+
+def dump_outputs(out_dir: str, outs: dict) -> None:
+    """--dump-outputs: every output buffer of the last timed step as out_dir/<name>.npy, float32
+    (byte values 0-255 are exact in it).  A buffer of more than DUMP_SAMPLE bytes is written as the
+    bytes at DUMP_SAMPLE positions drawn once from a fixed seed (sorted, the same for every run and
+    build), so a mode's four buffers come to at most 4 x 12 MiB of float32."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in outs.items():
+        flat = t.reshape(-1).view(torch.uint8)
+        if flat.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(0x5EED)
+            idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), flat.cpu().numpy().astype(np.float32))
+
+
 def main():
     args = parse()
     if args.host_child:
@@ -1151,7 +1189,7 @@ def main():
         print(json.dumps({"long_records": long_records_leg(torch.device("cuda", 0))}), flush=True)
         return
     sampler = None
-    if (int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_power
+    if (args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_power
             and args.mode in ("aead", "xor") and not under_profiler()):
         sampler = start_power_sampler()  # before any GPU initialisation in this process
     import torch
@@ -1202,7 +1240,7 @@ def main():
         # Node::store_chunk(chunk_id, data) takes the id from its caller (ControlServer.cpp:1101
         # derives it beforehand): "given" ids take the fused one-pass kernel; "content" ids
         # (counter from the fresh digest) need the digest first, i.e. two passes
-        ids = (torch.randint(0, 256, (32 * n,), dtype=torch.uint8, device=dev)
+        ids = (torch.randint(0, 256, (32 * n,), dtype=torch.uint8, device=dev, generator=g)
                if args.store_ids == "given" else None)
 
     def seal():
@@ -1265,6 +1303,18 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if args.dump_outputs and rank == 0:
+        if args.mode == "wire":
+            outs = {"frames": frames, "opened": back, "macs": macs, "ok": ok}
+        elif args.mode == "store":
+            outs = {"ciphertext": ct, "hashes": hashes, "opened": back, "ok": ok}
+        elif args.mode == "xor":
+            outs = {"ciphertext": ct, "opened": back}
+        else:
+            outs = {"ciphertext": ct, "tags": tags, "opened": back, "ok": ok}
+        dump_outputs(args.dump_outputs, outs)
+
+    # From here to the result line only the round-trip check runs without --full.
     # per-kernel durations: HIP events on the launch stream bracketing back-to-back launches of
     # one kernel (separate from the timed region so the markers do not add kernel gaps there)
     # Timed in the same seal/open alternation as the timed region: each kernel reads what the
@@ -1283,8 +1333,8 @@ def main():
         o_ms = sum(ev[2 * i + 1].elapsed_time(ev[2 * i + 2]) for i in range(reps)) / reps
         return s_ms, o_ms
 
-    reps = max(4, args.steps)
-    seal_ms, open_ms = kernel_ms_alt(reps)
+    if args.full:
+        seal_ms, open_ms = kernel_ms_alt(max(4, args.steps))
     okh = int(ok.sum().item()) if args.mode != "xor" else n
     # the round trip must give the plaintext back, byte for byte (a keystream bug shared by seal
     # and open would still verify every tag), and the ciphertext must differ from it
@@ -1310,7 +1360,7 @@ def main():
     # host pipeline and BASELINE config 5 (mixed 512 B-64 KiB, AEAD + fused HMAC, H2D/D2H
     # included) at its per-GPU share, 524 288 / 8 = 65 536 records per rank, timed over all ranks
     host = None
-    if args.mode == "aead" and not args.no_host and (n, L) == (65536, 4096):
+    if args.full and args.mode == "aead" and not args.no_host and (n, L) == (65536, 4096):
         import ephemeralnet_amd as E2
         if args.no_e2e:
             hc2 = {"gibs": 0.0, "seal_gibs": 0.0, "open_gibs": 0.0}
@@ -1339,7 +1389,7 @@ def main():
             if fq is not None:
                 host["frame_queue"] = fq
     long_recs = None
-    if args.mode == "aead" and world == 1 and not args.no_long and (n, L) == (65536, 4096):
+    if args.full and args.mode == "aead" and world == 1 and not args.no_long and (n, L) == (65536, 4096):
         long_recs = long_records_leg(dev)
     # every rank's placement (node, CPUs, CPU share) and its C5 share's pinned bytes / staging node
     placements = gather_placement(world, {**PLACEMENT_SHORT(), "c5_host": host.get("c5_host") if host else None})
@@ -1347,9 +1397,9 @@ def main():
         for r_, p_ in zip(ranks, placements):
             r_.update({k: v for k, v in p_.items() if k != "rank"})
 
-    if rank == 0:
-        total_bytes = n * L * args.steps * world
-        value = total_bytes / elapsed / 2**30
+    def kernel_report() -> dict:
+        """--full: the per-kernel keys of the result line, from seal_ms / open_ms and the recorded
+        counters under profiles/."""
         # algorithmic HBM bytes per launch (SURVEY.md 8d): seal 2L+64, open 2L+65 per record
         # (xor: 2L + key/nonce/counter 48; wire: frames carry 48 more bytes; store: hashes/ids)
         seal_bytes = n * (2 * L + {"aead": 64, "xor": 48, "wire": 92, "store": 76}[args.mode]
@@ -1408,6 +1458,33 @@ def main():
                     valu["cycles_per_instr_per_simd_at_2.4GHz"] = round(
                         dom_s * 2.4e9 * 1024 / k["SQ_INSTS_VALU"], 2)
                     valu["pmc_source"] = pmc_note
+        return {
+            "seal_ms": round(seal_ms, 4),
+            "open_ms": round(open_ms, 4),
+            "seal_gibs": round(n * L / (seal_ms * 1e-3) / 2**30, 1),
+            "open_gibs": round(n * L / (open_ms * 1e-3) / 2**30, 1),
+            "roofline": {
+                "bound": "hbm",
+                "kernel": (f"stream_kernel ({dom})" if args.mode in ("aead", "xor")
+                           else f"{args.mode} {dom} kernel sequence"),
+                "achieved": round(dom_gbs, 1),
+                "peak": HBM_PEAK_GBS,
+                "unit": "GB/s",
+                "frac": round(dom_gbs / HBM_PEAK_GBS, 4),
+                "traffic": traffic,
+                "traffic_source": pmc_note,
+                "algorithmic_bytes_per_launch": seal_bytes if dom == "seal" else open_bytes,
+                "note": "power-capped: with the keystream and HBM streaming together the package sits "
+                        "at ~1.38 kW and the shader clock drops to ~2.08 GHz (2.39 GHz with either alone); "
+                        "in shader cycles the kernel is within 5 % of its compute-only form "
+                        "(profiles/r02_power.txt); VALU work: see valu_roofline",
+            },
+            "valu_roofline": valu,
+        }
+
+    if rank == 0:
+        total_bytes = n * L * args.steps * world
+        value = total_bytes / elapsed / 2**30
         out = {
             "metric": METRICS[args.mode],
             "value": round(value, 2),
@@ -1433,28 +1510,9 @@ def main():
                 "parallelism": f"records split over {world} GPU(s), no collective",
                 **({"chunk_ids": args.store_ids} if args.mode == "store" else {}),
             },
-            "seal_ms": round(seal_ms, 4),
-            "open_ms": round(open_ms, 4),
-            "seal_gibs": round(n * L / (seal_ms * 1e-3) / 2**30, 1),
-            "open_gibs": round(n * L / (open_ms * 1e-3) / 2**30, 1),
-            "roofline": {
-                "bound": "hbm",
-                "kernel": (f"stream_kernel ({dom})" if args.mode in ("aead", "xor")
-                           else f"{args.mode} {dom} kernel sequence"),
-                "achieved": round(dom_gbs, 1),
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": round(dom_gbs / HBM_PEAK_GBS, 4),
-                "traffic": traffic,
-                "traffic_source": pmc_note,
-                "algorithmic_bytes_per_launch": seal_bytes if dom == "seal" else open_bytes,
-                "note": "power-capped: with the keystream and HBM streaming together the package sits "
-                        "at ~1.38 kW and the shader clock drops to ~2.08 GHz (2.39 GHz with either alone); "
-                        "in shader cycles the kernel is within 5 % of its compute-only form "
-                        "(profiles/r02_power.txt); VALU work: see valu_roofline",
-            },
-            "valu_roofline": valu,
         }
+        if args.full:
+            out.update(kernel_report())
         if power:
             out["power"] = power
         if long_recs:
@@ -1467,7 +1525,7 @@ def main():
         if ranks is not None:
             out["dist"] = {"backend": dist.get_backend(), "world_size": dist.get_world_size(),
                            "per_rank": ranks}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             if args.mode == "wire":  # the same workload through the reference itself
                 ref = cpu_reference_frames(L, args.cpu_seconds)
                 if ref is not None:

@@ -19,10 +19,10 @@ step smoke
 timeout -k 10 240 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
 tail -1 $O/smoke.log
 step bench default
-timeout -k 10 240 python bench.py > $O/bench.json 2> $O/bench.err
+timeout -k 10 240 python bench.py --full > $O/bench.json 2> $O/bench.err
 cat $O/bench.json
 step torchrun path
-timeout -k 10 240 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --steps 50 --warmup 10 --no-cpu-baseline > $O/bench_torchrun.json 2> $O/bench_torchrun.err
+timeout -k 10 240 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --steps 50 --warmup 10 --full --no-cpu-baseline > $O/bench_torchrun.json 2> $O/bench_torchrun.err
 cat $O/bench_torchrun.json
 step side configs
 : > $O/side.jsonl
@@ -33,7 +33,7 @@ for args in "--records 1048576 --record-bytes 1500" "--records 32768 --record-by
             "--c5-device --records 65536" "--c5-device --records 65536 --c5-overlap" \
             "--c5-device --records 65536 --c5-order none"; do
   step "  $args"
-  timeout -k 10 400 python bench.py --steps 100 --warmup 20 $(case "$args" in *pow*|*1048576*|*c5*|*32768*) echo "--steps 10 --warmup 3";; esac) $(case "$args" in *pow*|*wire*) ;; *) echo --no-cpu-baseline;; esac) $args >> $O/side.jsonl 2>> $O/side.err
+  timeout -k 10 400 python bench.py --full --steps 100 --warmup 20 $(case "$args" in *pow*|*1048576*|*c5*|*32768*) echo "--steps 10 --warmup 3";; esac) $(case "$args" in *pow*|*wire*) ;; *) echo --no-cpu-baseline;; esac) $args >> $O/side.jsonl 2>> $O/side.err
 done
 step scalar latency
 for pol in auto device; do

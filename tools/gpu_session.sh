@@ -58,7 +58,7 @@ verify)
   step rehearse n2
   timeout -k 10 500 bash tools/gpu_rehearse_n2.sh $T/n2 > $O/n2.log 2>&1 || { tail -20 $O/n2.log; exit 1; }
   step bench
-  timeout -k 10 300 python bench.py > $O/bench.json 2> $O/bench.err
+  timeout -k 10 300 python bench.py --full > $O/bench.json 2> $O/bench.err
   cut -c1-400 $O/bench.json ;;
 queue)
   CPUS=$(node_cpus); : > $O/queue_bench.jsonl
@@ -114,7 +114,7 @@ c5-full)
 variance)
   : > $O/bench_repeat.jsonl
   for r in 1 2 3 4 5; do
-    timeout -k 10 300 python bench.py --no-cpu-baseline $( [ $r -gt 1 ] && echo --no-host ) >> $O/bench_repeat.jsonl 2>> $O/bench_repeat.err
+    timeout -k 10 300 python bench.py --full --no-cpu-baseline $( [ $r -gt 1 ] && echo --no-host ) >> $O/bench_repeat.jsonl 2>> $O/bench_repeat.err
   done
   python -c "
 import json
