@@ -1,5 +1,6 @@
 // capi.cpp -- the extern "C" boundary (include/enet_crypto.h): argument checks, lane
-// scheduling, and the kernel sequences for the composite operations (frames).
+// scheduling, and the kernel sequences for the composite operations (frames).  The record
+// launches themselves, with the routing of long records, are long_records.cpp's run_records.
 #include "enet_crypto.h"
 
 #include <hip/hip_runtime.h>
@@ -9,18 +10,18 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 #include <string>
 #include <vector>
 
 #include "enet_internal.hpp"
+#include "long_records.hpp"
 
 // nonce(12) || BE32 length (SessionManager.cpp:85-86,376-385)
 constexpr uint32_t kWireHeader = 16;
 
-namespace {
+static thread_local std::string g_last_error;
 
-thread_local std::string g_last_error;
+namespace enet {
 
 int fail(int code, const char* what) {
     g_last_error = what;
@@ -34,6 +35,19 @@ int hip_status(hipError_t e, const char* what) {
     }
     g_last_error = std::string(what) + ": " + hipGetErrorString(e);
     return ENET_EHIP;
+}
+
+}  // namespace enet
+
+namespace {
+
+using enet::fail;
+using enet::hip_status;
+using enet::run_records;
+
+// the two-pass paths' steps: "<name><step>" only when the launch failed
+int hip_status(hipError_t e, const char* name, const char* step) {
+    return hip_status(e, e == hipSuccess ? "" : (std::string(name) + step).c_str());
 }
 
 bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
@@ -78,10 +92,7 @@ enet::RecParams rec_params(const enet_records* r) {
     p.key_stride = r->key_stride;
     p.nonces = r->nonces;
     p.order = r->order;
-    // hints say every record has the same length: total == n * max (record i then starts at
-    // offsets[0] + i * max, since records are contiguous by construction)
-    if (r->max_len_hint && r->total_bytes_hint == (uint64_t)r->count * r->max_len_hint)
-        p.uniform_len = r->max_len_hint;
+    if (r->max_len_hint && enet::hints_uniform(r)) p.uniform_len = r->max_len_hint;
     p.coop = (int)enet::staging_variant();
     // variant 1 (default): line staging for unaligned one-lane records, lockstep keystream in
     // 512-thread workgroups otherwise; 4 = plain run staging (neither); 5 = lockstep run staging
@@ -147,7 +158,7 @@ enet::DuplexParams duplex_params(const enet_records* r) {
     p.key_stride = r->key_stride;
     p.nonces = r->nonces;
     p.order = r->order;
-    p.uniform = r->max_len_hint && r->total_bytes_hint == (uint64_t)r->count * r->max_len_hint;
+    p.uniform = r->max_len_hint && enet::hints_uniform(r);
     p.max_len = r->max_len_hint;
     return p;
 }
@@ -156,246 +167,78 @@ uint32_t lanes_for(const enet_records* r) {
     return enet::choose_lanes(r->count, r->total_bytes_hint, r->max_len_hint);
 }
 
-// ---- the sequence-parallel path (segments.hip) for long records
-// -1: auto (below); otherwise every record of at least this many bytes takes the tiles, whatever
-// the hints say (enet_set_seg_min: tests / tuning; INT64_MAX = never)
-std::atomic<int64_t> g_seg_min{-1};
-std::atomic<uint64_t> g_seg_batches{0};  // batches that took the tiles (enet_seg_batches)
-
-// Auto: a batch whose longest record (hint) is >= kSegMin takes the tiles for its records >=
-// kSegMin -- unless it is uniform and wide enough that 16 lanes per record already fill the chip
-// (n * 16 >= 131 072 lanes: the record / streaming kernels run those at the C2 rate).
-bool seg_wanted(const enet_records* r, uint64_t& long_min) {
-    const int64_t f = g_seg_min.load(std::memory_order_relaxed);
-    if (f >= 0) {
-        long_min = (uint64_t)f;
-        return f != INT64_MAX;
-    }
-    long_min = enet::kSegMin;
-    if (r->max_len_hint < enet::kSegMin) return false;
-    const bool uniform = r->total_bytes_hint == (uint64_t)r->count * r->max_len_hint;
-    return !(uniform && (uint64_t)r->count * enet::kMaxLanesPerRecord >= 131072u);
+// ---- the two-pass paths (hash kernel + records kernel), taken when duplex_on() is false
+// The hash pass over the batch's input (or, after the cipher pass, output) records, in the
+// batch's order; hmac: HMAC-SHA256 under the records' keys, otherwise plain SHA-256
+enet::ShaParams sha_over(const enet_records* r, bool output_side, bool hmac) {
+    enet::ShaParams s{};
+    s.n = r->count;
+    s.in = output_side ? r->out : r->in;
+    s.off = output_side ? r->out_offsets : r->in_offsets;
+    s.keys = hmac ? r->keys : nullptr;
+    s.key_stride = hmac ? r->key_stride : 0;
+    s.order = r->order;
+    return s;
 }
 
-// Scratch comes from a library-private, stream-ordered pool per device (hipMallocFromPoolAsync /
-// hipFreeAsync on the caller's stream): no synchronisation, capturable, and concurrent calls on
-// different streams get their own.  Freed memory stays in the pool.
-hipMemPool_t seg_pool() {
-    static std::mutex mu;
-    static hipMemPool_t pools[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-    std::lock_guard<std::mutex> lk(mu);
-    if (!pools[dev]) {
-        hipMemPoolProps props{};
-        props.allocType = hipMemAllocationTypePinned;
-        props.location.type = hipMemLocationTypeDevice;
-        props.location.id = dev;
-        hipMemPool_t pl = nullptr;
-        if (hipMemPoolCreate(&pl, &props) != hipSuccess) return nullptr;
-        uint64_t keep = UINT64_MAX;
-        (void)hipMemPoolSetAttribute(pl, hipMemPoolAttrReleaseThreshold, &keep);
-        pools[dev] = pl;
+// Frames (hdr 0) and wire frames (hdr kWireHeader); name ("frame_seal", "wire_open", ...)
+// starts every error text.
+int frame_seal(const enet_records* r, uint32_t hdr, hipStream_t st, const char* name) {
+    if (int e = check_records(r, true)) return e;
+    if (r->count == 0) return ENET_OK;
+    if (duplex_on()) {
+        enet::DuplexParams d = duplex_params(r);
+        d.hdr = hdr;
+        return hip_status(enet::launch_duplex(enet::DK_FRAME, false, d, st), name, " duplex");
     }
-    return pools[dev];
+    // 1) MAC = HMAC-SHA256(K, m) written in clear at the tail of each frame body
+    enet::ShaParams s = sha_over(r, false, true);
+    s.digest = r->out + hdr;
+    s.dest_off = r->out_offsets;
+    if (int e = hip_status(enet::launch_sha(s, st), name, " hmac launch")) return e;
+    // 2) [header +] body = ChaCha20(ctr 0) over m || MAC
+    enet::RecParams p = rec_params(r);
+    p.hdr = hdr;
+    return hip_status(enet::launch_records(3, p, lanes_for(r), st), name, " chacha launch");
 }
 
-struct SegRun {
-    void* mem = nullptr;
-    const uint8_t* claimed = nullptr;
-};
-
-// Per-stream state of the one-launch AEAD path (segments.hip seg_uniform_aead_kernel): arrival
-// counters, zeroed when allocated and reset by each record's last arriver, so they are zero
-// whenever a launch on that stream starts (launches on one stream run in order); and the tiles'
-// partials.  Grown on demand, stream-ordered; otherwise reused, so a launch makes no allocation
-// (a stream-ordered allocate / free pair per call cost ~4 us of gap between launches).
-struct Arrivals {
-    uint32_t* ptr = nullptr;
-    uint32_t cap = 0;
-    void* part = nullptr;
-    size_t part_cap = 0;
-    void* seg = nullptr;  // the plan + tiles path's scratch (seg_begin)
-    size_t seg_cap = 0;
-};
-
-int arrivals_for(hipStream_t st, uint32_t n, uint32_t*& out, size_t part_bytes = 0, void** part_out = nullptr,
-                 size_t seg_bytes = 0, void** seg_out = nullptr) {
-    static std::mutex mu;
-    static std::vector<std::pair<std::pair<int, hipStream_t>, Arrivals>> table;
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev)) return hip_status(e, "aead tiles: hipGetDevice");
-    std::lock_guard<std::mutex> lk(mu);
-    Arrivals* a = nullptr;
-    for (auto& kv : table)
-        if (kv.first.first == dev && kv.first.second == st) a = &kv.second;
-    if (!a) {
-        table.push_back({{dev, st}, Arrivals{}});
-        a = &table.back().second;
+int frame_open(const enet_records* r, uint32_t hdr, uint8_t* macs, uint8_t* ok, hipStream_t st, const char* name) {
+    if (int e = check_records(r, true)) return e;
+    if (r->count == 0) return ENET_OK;
+    if (!macs || !ok || !aligned4(macs))
+        return fail(ENET_EINVAL, (std::string(name) + ": NULL/misaligned macs or NULL ok").c_str());
+    if (duplex_on()) {
+        enet::DuplexParams d = duplex_params(r);
+        d.hdr = hdr;
+        d.macs = macs;
+        d.ok = ok;
+        return hip_status(enet::launch_duplex(enet::DK_FRAME, true, d, st), name, " duplex");
     }
-    if (a->cap < n) {
-        hipMemPool_t pool = seg_pool();
-        if (!pool) return fail(ENET_EHIP, "aead tiles: no memory pool for the current device");
-        const uint32_t cap = std::max<uint32_t>(n, 1024u);
-        void* mem = nullptr;
-        if (hipError_t e = hipMallocFromPoolAsync(&mem, 4ull * cap, pool, st)) return hip_status(e, "aead tiles: counters");
-        if (hipError_t e = hipMemsetAsync(mem, 0, 4ull * cap, st)) return hip_status(e, "aead tiles: counters");
-        if (a->ptr) (void)hipFreeAsync(a->ptr, st);
-        a->ptr = static_cast<uint32_t*>(mem);
-        a->cap = cap;
+    // 1) decrypt: message bytes to out, MAC bytes to macs (wire: the nonce read from the header)
+    enet::RecParams p = rec_params(r);
+    if (hdr) p.nonces = nullptr;
+    p.hdr = hdr;
+    p.tag_out = macs;
+    if (int e = hip_status(enet::launch_records(4, p, lanes_for(r), st), name, " chacha")) return e;
+    // 2) verify HMAC over the decrypted message; zero the message on failure
+    enet::ShaParams s = sha_over(r, true, true);
+    s.expect = macs;
+    s.ok = ok;
+    s.guard_off = r->in_offsets;
+    if (hdr) {
+        s.wire_in = r->in;
+        s.wire_hdr = hdr;
     }
-    if (part_out && a->part_cap < part_bytes) {
-        hipMemPool_t pool = seg_pool();
-        if (!pool) return fail(ENET_EHIP, "aead tiles: no memory pool for the current device");
-        const size_t cap = std::max<size_t>(part_bytes, 64u << 10);
-        void* mem = nullptr;
-        if (hipError_t e = hipMallocFromPoolAsync(&mem, cap, pool, st)) return hip_status(e, "aead tiles: scratch");
-        if (a->part) (void)hipFreeAsync(a->part, st);
-        a->part = mem;
-        a->part_cap = cap;
-    }
-    if (part_out) *part_out = a->part;
-    if (seg_out && a->seg_cap < seg_bytes) {
-        hipMemPool_t pool = seg_pool();
-        if (!pool) return fail(ENET_EHIP, "sequence-parallel scratch: no memory pool for the current device");
-        const size_t cap = std::max<size_t>(seg_bytes, 256u << 10);
-        void* mem = nullptr;
-        if (hipError_t e = hipMallocFromPoolAsync(&mem, cap, pool, st)) return hip_status(e, "sequence-parallel scratch");
-        if (a->seg) (void)hipFreeAsync(a->seg, st);
-        a->seg = mem;
-        a->seg_cap = cap;
-    }
-    if (seg_out) *seg_out = a->seg;
-    out = a->ptr;
-    return ENET_OK;
+    s.zero_on_fail = r->out;
+    return hip_status(enet::launch_sha(s, st), name, " hmac verify");
 }
 
-// RFC 8439 seal / open over a batch the hints call uniform and long: one launch
-int run_uniform_aead(int mode, const enet_records* r, const enet::RecParams& p, hipStream_t st, const char* what) {
-    const uint64_t L = r->max_len_hint;
-    const uint64_t T = (L + enet::kSegTileBytes - 1) / enet::kSegTileBytes;
-    const uint64_t tiles = (uint64_t)r->count * T;
-    uint32_t* arr = nullptr;
-    const uint64_t words = (uint64_t)r->count * enet::seg_uniform_arrival_words();
-    if (words > UINT32_MAX) return fail(ENET_EINVAL, "aead tiles: too many records for one launch");
-    void* mem = nullptr;
-    if (int e = arrivals_for(st, (uint32_t)words, arr, (size_t)tiles * 32, &mem)) return e;
-    enet::SegParams q{};
-    q.mode = mode;
-    q.n = r->count;
-    q.in_off = p.in_off;
-    q.out_off = p.out_off;
-    q.in = p.in;
-    q.out = p.out;
-    q.keys = p.keys;
-    q.key_stride = p.key_stride;
-    q.nonces = p.nonces;
-    q.aad = p.aad;
-    q.aad_off = p.aad_off;
-    q.tag_in = p.tag_in;
-    q.tag_out = p.tag_out;
-    q.ok = p.ok;
-    q.partials = static_cast<uint32_t*>(mem);
-    g_seg_batches.fetch_add(1, std::memory_order_relaxed);
-    return hip_status(enet::launch_seg_uniform_aead(q, L, arr, st), what);
-}
-
-// Plan + tile kernels for the batch's long records; sr.claimed marks them for the record engine.
-// index_n: one past the largest record index (r->count unless r->order names a subset).
-int seg_begin(int mode, const enet_records* r, enet::RecParams& p, uint64_t long_min, hipStream_t st,
-              SegRun& sr, uint32_t index_n) {
-    const uint32_t n = r->count;
-    const uint64_t total = r->total_bytes_hint ? r->total_bytes_hint
-                                               : (uint64_t)std::min<uint32_t>(n, 1024u) * r->max_len_hint;
-    // capacities from the hints; records past them stay with the record engine (never wrong bytes)
-    const uint64_t ecap = std::min<uint64_t>(n, long_min ? total / long_min + 1 : n);
-    const uint64_t tcap = std::min<uint64_t>(total / enet::kSegTileBytes + ecap + 1, 0xFFFFFFFFull);
-    const size_t o_ent = 256, o_cl = o_ent + (size_t)ecap * sizeof(enet::SegEntry),
-                 o_part = (o_cl + index_n + 255) & ~size_t(255), bytes = o_part + (size_t)tcap * 32;
-    // per-stream scratch, reused: one seg run per call, calls on a stream run in order, and the
-    // plan kernel initialises everything the tiles read (no allocate / free pair per call)
-    uint32_t* unused = nullptr;
-    void* mem = nullptr;
-    if (int e = arrivals_for(st, 0, unused, 0, nullptr, bytes, &mem)) return e;
-    uint8_t* base = static_cast<uint8_t*>(mem);
-    enet::SegParams q{};
-    q.mode = mode;
-    q.n = n;
-    q.in_off = p.in_off;
-    q.out_off = p.out_off;
-    q.in = p.in;
-    q.out = p.out;
-    q.keys = p.keys;
-    q.key_stride = p.key_stride;
-    q.nonces = p.nonces;
-    q.counters = p.counters;
-    q.counter_stride = p.counter_stride;
-    q.aad = p.aad;
-    q.aad_off = p.aad_off;
-    q.tag_in = p.tag_in;
-    q.tag_out = p.tag_out;
-    q.ok = p.ok;
-    q.order = p.order;
-    q.hdr = reinterpret_cast<unsigned long long*>(base);
-    q.entries = reinterpret_cast<enet::SegEntry*>(base + o_ent);
-    q.claimed = base + o_cl;
-    q.partials = reinterpret_cast<uint32_t*>(base + o_part);
-    q.entry_cap = (uint32_t)ecap;
-    q.tile_cap = (uint32_t)tcap;
-    q.long_min = long_min;
-    const uint32_t plan_blocks = (uint32_t)std::min<uint64_t>((n + 255) / 256, 1024);
-    const uint32_t tile_blocks = (uint32_t)std::min<uint64_t>(tcap, 4096);
-    sr.claimed = q.claimed;
-    g_seg_batches.fetch_add(1, std::memory_order_relaxed);
-    return hip_status(enet::launch_seg(q, plan_blocks, tile_blocks, st), "sequence-parallel launch");
-}
-
-void seg_end(SegRun& sr, hipStream_t st) {
-    (void)sr;
-    (void)st;
-}
-
-// The record engine over the batch, with the long records on the tiles first when seg_wanted
-int run_records(int mode, const enet_records* r, enet::RecParams& p, hipStream_t st, const char* what,
-                uint32_t index_n = 0) {
-    uint64_t long_min = 0;
-    SegRun sr;
-    // XOR over a batch the hints call uniform and long: one launch of tile workgroups, nothing
-    // else (a record that is not as hinted is run whole by its tile-0 workgroup)
-    if (mode == enet::MODE_XOR && !r->order && seg_wanted(r, long_min) && r->max_len_hint >= long_min &&
-        r->total_bytes_hint == (uint64_t)r->count * r->max_len_hint) {
-        enet::SegParams q{};
-        q.mode = mode;
-        q.n = r->count;
-        q.in_off = p.in_off;
-        q.out_off = p.out_off;
-        q.in = p.in;
-        q.out = p.out;
-        q.keys = p.keys;
-        q.key_stride = p.key_stride;
-        q.nonces = p.nonces;
-        q.counters = p.counters;
-        q.counter_stride = p.counter_stride;
-        g_seg_batches.fetch_add(1, std::memory_order_relaxed);
-        return hip_status(enet::launch_seg_uniform_xor(q, r->max_len_hint, st), what);
-    }
-    // AEAD over such a batch: one launch too (the last tile of each record to arrive combines,
-    // and zeroes a failed open itself)
-    if ((mode == enet::MODE_SEAL || mode == enet::MODE_OPEN) && !r->order && seg_wanted(r, long_min) &&
-        r->max_len_hint >= long_min && r->total_bytes_hint == (uint64_t)r->count * r->max_len_hint &&
-        (uint64_t)r->count * ((r->max_len_hint + enet::kSegTileBytes - 1) / enet::kSegTileBytes) < 0x7FFFFFFFull)
-        return run_uniform_aead(mode, r, p, st, what);
-    if (mode <= enet::MODE_OPEN && seg_wanted(r, long_min)) {
-        if (int e = seg_begin(mode, r, p, long_min, st, sr, index_n ? index_n : r->count)) {
-            seg_end(sr, st);
-            return e;
-        }
-        p.skip = sr.claimed;
-        p.uniform_len = 0;  // per-lane path: the staged paths assume every record is theirs
-    }
-    const int rc = hip_status(enet::launch_records(mode, p, lanes_for(r), st), what);
-    seg_end(sr, st);
-    return rc;
+// wire open reads each nonce from its frame: the descriptor may leave nonces NULL
+enet_records with_frame_nonce(const enet_records* r) {
+    static const uint32_t kNoNonce[3] = {0, 0, 0};
+    enet_records q = *r;
+    if (!q.nonces) q.nonces = reinterpret_cast<const uint8_t*>(kNoNonce);
+    return q;
 }
 
 // ---- chunk store / fetch on the device (every record on the GPU)
@@ -408,12 +251,8 @@ int chunk_store_device(const enet_records* r, const uint8_t* chunk_ids, uint8_t*
         return hip_status(enet::launch_duplex(enet::DK_CHUNK, false, d, st), "chunk_store duplex");
     }
     // 1) chunk_hash = SHA-256(pt) (Node.cpp:1414; = derive_chunk_id, StoreProof.cpp:75-78)
-    enet::ShaParams s{};
-    s.n = r->count;
-    s.in = r->in;
-    s.off = r->in_offsets;
+    enet::ShaParams s = sha_over(r, false, false);
     s.digest = chunk_hashes;
-    s.order = r->order;
     if (int e = hip_status(enet::launch_sha(s, st), "chunk_store sha")) return e;
     // 2) ChaCha20 from counter LE32(chunk_id[0..3]) (CryptoManager.cpp:8-13,38-46), the id read
     //    on the device (the fresh digests when the caller derives ids from content)
@@ -441,14 +280,10 @@ int chunk_fetch_device(const enet_records* r, const uint8_t* chunk_ids, const ui
                            "chunk_fetch chacha"))
         return e;
     // 2) SHA-256(pt) == manifest.chunk_hash, else no plaintext (Node.cpp:1644-1655)
-    enet::ShaParams s{};
-    s.n = r->count;
-    s.in = r->out;
-    s.off = r->out_offsets;
+    enet::ShaParams s = sha_over(r, true, false);
     s.expect = chunk_hashes;
     s.ok = ok;
     s.zero_on_fail = r->out;
-    s.order = r->order;
     return hip_status(enet::launch_sha(s, st), "chunk_fetch sha verify");
 }
 
@@ -545,7 +380,7 @@ int chunk_scratch(const LongSplit& ls, hipStream_t st, ChunkScratch& cs) {
     const size_t ns = ls.shorts.size(), m = ls.longs.size();
     const size_t o_l = (4 * ns + 255) & ~size_t(255), o_r = (o_l + 4 * m + 255) & ~size_t(255),
                  bytes = o_r + 32 * m;
-    hipMemPool_t pool = seg_pool();
+    hipMemPool_t pool = enet::scratch_pool();
     if (!pool) return fail(ENET_EHIP, "chunk: no memory pool for the current device");
     void* d = nullptr;
     if (hipError_t e = hipMallocFromPoolAsync(&d, bytes, pool, st)) return hip_status(e, "chunk scratch");
@@ -741,11 +576,11 @@ int enet_set_duplex_split(int mode) {
 
 int enet_set_seg_min(int64_t bytes) {
     if (bytes < -1) return fail(ENET_EINVAL, "seg_min must be -1 (auto), 0 .. INT64_MAX");
-    g_seg_min.store(bytes, std::memory_order_relaxed);
+    enet::set_seg_min(bytes);
     return ENET_OK;
 }
 
-uint64_t enet_seg_batches(void) { return g_seg_batches.load(std::memory_order_relaxed); }
+uint64_t enet_seg_batches(void) { return enet::seg_batches(); }
 
 int enet_set_lanes_per_record(uint32_t lanes) {
     if (lanes != 0 && lanes != 1 && lanes != 2 && lanes != 4 && lanes != 8 && lanes != 16)
@@ -856,14 +691,8 @@ int enet_aead_hmac_seal_batch(const enet_records* r, uint8_t* tags, uint8_t* mac
         return hip_status(enet::launch_duplex(enet::DK_AEADH, false, d, st), "aead_hmac_seal duplex");
     }
     // two-pass: HMAC over the plaintext (encode_signed semantics), then the AEAD pass
-    enet::ShaParams s{};
-    s.n = r->count;
-    s.in = r->in;
-    s.off = r->in_offsets;
+    enet::ShaParams s = sha_over(r, false, true);
     s.digest = macs;
-    s.keys = r->keys;
-    s.key_stride = r->key_stride;
-    s.order = r->order;
     if (int e = hip_status(enet::launch_sha(s, st), "aead_hmac_seal hmac")) return e;
     enet::RecParams p = rec_params(r);
     p.tag_out = tags;
@@ -892,73 +721,20 @@ int enet_aead_hmac_open_batch(const enet_records* r, const uint8_t* tags, const 
                            "aead_hmac_open aead"))
         return e;
     // HMAC verify over the decrypted plaintext, AND-ed into ok; zero the record on failure
-    enet::ShaParams s{};
-    s.n = r->count;
-    s.in = r->out;
-    s.off = r->out_offsets;
-    s.keys = r->keys;
-    s.key_stride = r->key_stride;
+    enet::ShaParams s = sha_over(r, true, true);
     s.expect = macs;
     s.ok = ok;
     s.and_ok = 1;
     s.zero_on_fail = r->out;
-    s.order = r->order;
     return hip_status(enet::launch_sha(s, st), "aead_hmac_open hmac verify");
 }
 
 int enet_frame_seal_batch(const enet_records* r, void* stream) {
-    if (int e = check_records(r, true)) return e;
-    if (r->count == 0) return ENET_OK;
-    if (duplex_on()) {
-        enet::DuplexParams d = duplex_params(r);
-        return hip_status(enet::launch_duplex(enet::DK_FRAME, false, d, (hipStream_t)stream), "frame_seal duplex");
-    }
-    // 1) MAC = HMAC-SHA256(K, m) written in clear at the tail of each output record
-    enet::ShaParams s{};
-    s.n = r->count;
-    s.in = r->in;
-    s.off = r->in_offsets;
-    s.digest = r->out;
-    s.dest_off = r->out_offsets;
-    s.keys = r->keys;
-    s.key_stride = r->key_stride;
-    s.order = r->order;
-    hipStream_t st = (hipStream_t)stream;
-    if (int e = hip_status(enet::launch_sha(s, st), "frame_seal hmac launch")) return e;
-    // 2) body = ChaCha20(ctr 0) over m || MAC
-    enet::RecParams p = rec_params(r);
-    return hip_status(enet::launch_records(3, p, lanes_for(r), st), "frame_seal chacha launch");
+    return frame_seal(r, 0, (hipStream_t)stream, "frame_seal");
 }
 
 int enet_frame_open_batch(const enet_records* r, uint8_t* macs, uint8_t* ok, void* stream) {
-    if (int e = check_records(r, true)) return e;
-    if (r->count == 0) return ENET_OK;
-    if (!macs || !ok || !aligned4(macs)) return fail(ENET_EINVAL, "frame_open: NULL/misaligned macs or NULL ok");
-    hipStream_t st = (hipStream_t)stream;
-    if (duplex_on()) {
-        enet::DuplexParams d = duplex_params(r);
-        d.macs = macs;
-        d.ok = ok;
-        return hip_status(enet::launch_duplex(enet::DK_FRAME, true, d, st), "frame_open duplex");
-    }
-    // 1) decrypt: message bytes to out, MAC bytes to macs
-    enet::RecParams p = rec_params(r);
-    p.tag_out = macs;
-    if (int e = hip_status(enet::launch_records(4, p, lanes_for(r), st), "frame_open chacha"))
-        return e;
-    // 2) verify HMAC over the decrypted message; zero the message on failure
-    enet::ShaParams s{};
-    s.n = r->count;
-    s.in = r->out;
-    s.off = r->out_offsets;
-    s.keys = r->keys;
-    s.key_stride = r->key_stride;
-    s.expect = macs;
-    s.ok = ok;
-    s.guard_off = r->in_offsets;
-    s.zero_on_fail = r->out;
-    s.order = r->order;
-    return hip_status(enet::launch_sha(s, st), "frame_open hmac verify");
+    return frame_open(r, 0, macs, ok, (hipStream_t)stream, "frame_open");
 }
 
 int enet_chunk_store_batch(const enet_records* r, const uint8_t* chunk_ids, uint8_t* chunk_hashes,
@@ -1007,29 +783,7 @@ int enet_set_host_hash_min(int64_t bytes) {
 uint64_t enet_host_hash_batches(void) { return g_hh_batches.load(std::memory_order_relaxed); }
 
 int enet_wire_seal_batch(const enet_records* r, void* stream) {
-    if (int e = check_records(r, true)) return e;
-    if (r->count == 0) return ENET_OK;
-    hipStream_t st = (hipStream_t)stream;
-    if (duplex_on()) {
-        enet::DuplexParams d = duplex_params(r);
-        d.hdr = kWireHeader;
-        return hip_status(enet::launch_duplex(enet::DK_FRAME, false, d, st), "wire_seal duplex");
-    }
-    // 1) MAC = HMAC-SHA256(K, m) in clear at the tail of each frame body
-    enet::ShaParams s{};
-    s.n = r->count;
-    s.in = r->in;
-    s.off = r->in_offsets;
-    s.digest = r->out + kWireHeader;
-    s.dest_off = r->out_offsets;
-    s.keys = r->keys;
-    s.key_stride = r->key_stride;
-    s.order = r->order;
-    if (int e = hip_status(enet::launch_sha(s, st), "wire_seal hmac launch")) return e;
-    // 2) header + body = ChaCha20(ctr 0) over m || MAC
-    enet::RecParams p = rec_params(r);
-    p.hdr = kWireHeader;
-    return hip_status(enet::launch_records(3, p, lanes_for(r), st), "wire_seal chacha launch");
+    return frame_seal(r, kWireHeader, (hipStream_t)stream, "wire_seal");
 }
 
 int enet_hmac_midstates(const uint8_t* keys, uint32_t n, uint32_t* mid, void* stream) {
@@ -1056,9 +810,7 @@ int enet_wire_open_batch_sessions(const enet_records* r, const uint32_t* session
                                   const uint32_t* mid, uint8_t* macs, uint8_t* ok, void* stream) {
     if (!r) return fail(ENET_EINVAL, "records descriptor is NULL");
     if (r->count == 0) return ENET_OK;
-    enet_records q = *r;
-    static const uint32_t kNoNonce[3] = {0, 0, 0};
-    if (!q.nonces) q.nonces = reinterpret_cast<const uint8_t*>(kNoNonce);  // read from frames
+    const enet_records q = with_frame_nonce(r);
     if (int e = check_records(&q, true)) return e;
     if (!macs || !ok || !aligned4(macs)) return fail(ENET_EINVAL, "wire_open_sessions: NULL/misaligned macs or NULL ok");
     if (!session || !mid || !aligned4(session) || !aligned4(mid) || sessions == 0) return fail(ENET_EINVAL, "wire_open_sessions: NULL/misaligned session or mid, or no sessions");
@@ -1074,40 +826,8 @@ int enet_wire_open_batch_sessions(const enet_records* r, const uint32_t* session
 
 int enet_wire_open_batch(const enet_records* r, uint8_t* macs, uint8_t* ok, void* stream) {
     if (!r) return fail(ENET_EINVAL, "records descriptor is NULL");
-    if (r->count == 0) return ENET_OK;
-    enet_records q = *r;
-    static const uint32_t kNoNonce[3] = {0, 0, 0};
-    if (!q.nonces) q.nonces = reinterpret_cast<const uint8_t*>(kNoNonce);  // read from frames
-    if (int e = check_records(&q, true)) return e;
-    if (!macs || !ok || !aligned4(macs)) return fail(ENET_EINVAL, "wire_open: NULL/misaligned macs or NULL ok");
-    hipStream_t st = (hipStream_t)stream;
-    if (duplex_on()) {
-        enet::DuplexParams d = duplex_params(&q);
-        d.hdr = kWireHeader;
-        d.macs = macs;
-        d.ok = ok;
-        return hip_status(enet::launch_duplex(enet::DK_FRAME, true, d, st), "wire_open duplex");
-    }
-    enet::RecParams p = rec_params(&q);
-    p.nonces = nullptr;
-    p.hdr = kWireHeader;
-    p.tag_out = macs;
-    if (int e = hip_status(enet::launch_records(4, p, lanes_for(r), st), "wire_open chacha"))
-        return e;
-    enet::ShaParams s{};
-    s.n = r->count;
-    s.in = r->out;
-    s.off = r->out_offsets;
-    s.keys = r->keys;
-    s.key_stride = r->key_stride;
-    s.expect = macs;
-    s.ok = ok;
-    s.guard_off = r->in_offsets;
-    s.wire_in = r->in;
-    s.wire_hdr = kWireHeader;
-    s.zero_on_fail = r->out;
-    s.order = r->order;
-    return hip_status(enet::launch_sha(s, st), "wire_open hmac verify");
+    const enet_records q = with_frame_nonce(r);
+    return frame_open(&q, kWireHeader, macs, ok, (hipStream_t)stream, "wire_open");
 }
 
 int enet_pow_search_batch(uint32_t n, const uint8_t* prefixes, const uint64_t* prefix_offsets,

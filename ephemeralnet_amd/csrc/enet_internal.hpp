@@ -6,12 +6,11 @@
 
 #include <string>
 
+#include "long_route.hpp"  // kMaxLanesPerRecord, RecMode, kSegMin, kSegTileBytes
+
 namespace enet {
 
 constexpr int kWG = 256;           // threads per workgroup (4 waves of 64)
-constexpr int kMaxLanesPerRecord = 16;
-
-enum RecMode : int { MODE_XOR = 0, MODE_SEAL = 1, MODE_OPEN = 2 };
 
 // Kernel parameters for the ChaCha20 / AEAD record engine (passed by value).
 struct RecParams {
@@ -166,8 +165,6 @@ struct SegEntry {
     uint32_t r[4], s[4];     // AEAD: one-time key halves (r unclamped words; s the pad)
     uint32_t pw[5 * 40];     // AEAD: r^(2^k) in 26-bit limbs, k < nbits
 };
-constexpr uint64_t kSegMin = 256u << 10;   // records this long take the tiles (seg_wanted)
-constexpr uint64_t kSegTileBytes = 64u << 10;
 constexpr uint64_t kSegMaxLen = 1ull << 35;  // 32-bit Poly1305 block positions inside a record
 struct SegParams {
     int mode;                  // MODE_XOR / MODE_SEAL / MODE_OPEN
@@ -187,7 +184,7 @@ struct SegParams {
     uint8_t* tag_out;
     uint8_t* ok;
     const uint32_t* order;     // nullable: the records to plan are order[0 .. n) (a subset)
-    // scratch (stream-ordered, capi.cpp seg_begin)
+    // scratch (stream-ordered, long_records.cpp seg_begin)
     unsigned long long* hdr;   // count << 40 | tiles claimed
     SegEntry* entries;         // [entry_cap]
     uint8_t* claimed;          // [index bound]: indexed by record

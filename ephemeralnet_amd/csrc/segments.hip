@@ -584,8 +584,8 @@ __global__ __launch_bounds__(kSegThreads) void seg_uniform_xor_kernel(SegParams 
 //     tree whose level multipliers are table entries, then h = Q r^R + P_last;
 //   * open: every tile stores its plaintext write-through (sc1) and drains it before arriving, so
 //     the last arriver can zero a failed record itself (no later pass needed);
-//   * the arrival counters are per-stream state, zero when the launch starts (capi.cpp) and reset
-//     by each record's last arriver;
+//   * the arrival counters are per-stream state, zero when the launch starts (long_records.cpp)
+//     and reset by each record's last arriver;
 //   * a record whose real length differs from the hint is run whole by its tile-0 workgroup, tile
 //     after tile, its partials combined in that workgroup (a wrong hint costs speed, never bytes).
 // TPW tiles per workgroup (4 TPW data waves) + the power wave.  Past one tile per CU, two tiles
