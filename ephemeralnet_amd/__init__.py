@@ -14,6 +14,7 @@ Operations mirror the reference src/crypto API, batched (ShardianLabs/EphemeralN
   pow_search/check compute_store_pow / compute_{announce,handshake}_pow and the *_valid checks
                   src/security/StoreProof.cpp:109-146, src/core/Node.cpp:193-292
   session_keys   KeyManager::derive_key     src/network/KeyManager.cpp:74-92
+  shamir_split/combine Shamir::split / combine src/crypto/Shamir.cpp:114-163
 """
 from __future__ import annotations
 
@@ -69,7 +70,7 @@ EXPORTS = [
     "enet_pipeline_group_aead_hmac_open", "enet_pow_search_batch", "enet_pow_check_batch", "enet_session_key_batch",
     "enet_host_mode_probe", "enet_host_mode_auto", "enet_host_mode_for", "enet_pipeline_stats", "enet_device_numa_node",
     "enet_host_cpu_budget", "enet_host_pinned_bytes", "enet_host_plan", "enet_host_register",
-    "enet_host_unregister",
+    "enet_host_unregister", "enet_shamir_split_batch", "enet_shamir_combine_batch",
 ]
 
 
@@ -200,6 +201,8 @@ def lib() -> C.CDLL:
         L.enet_host_plan.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, u32, u32, C.POINTER(HostPlan)]
         L.enet_host_register.argtypes = [vp, u64]
         L.enet_host_unregister.argtypes = [vp]
+        L.enet_shamir_split_batch.argtypes = [u32, vp, vp, u32, u32, vp, vp]
+        L.enet_shamir_combine_batch.argtypes = [u32, u32, vp, vp, vp, vp, vp]
         for name in EXPORTS:
             getattr(L, name)
         _lib = L
@@ -426,6 +429,25 @@ def session_keys(secrets, counters, ticks, out, stream=None) -> None:
     n = int(counters.numel())
     _check(lib().enet_session_key_batch(n, _ptr(secrets), _ptr(counters), _ptr(ticks), _ptr(out),
                                         _stream(stream)), "enet_session_key_batch")
+
+
+def shamir_split(secrets, coeffs, threshold: int, share_count: int, shares, stream=None) -> None:
+    """Shamir::split for a batch (Shamir.cpp:114-150): secrets uint8 [n,32]; coeffs uint8
+    [n,threshold-1,32] random bytes (None when threshold == 1); shares uint8 [n,share_count,32],
+    share j of record i (index j+1) at shares[i,j]."""
+    n = int(secrets.numel()) // 32
+    _check(lib().enet_shamir_split_batch(n, _ptr(secrets), _ptr(coeffs), int(threshold), int(share_count),
+                                         _ptr(shares), _stream(stream)), "enet_shamir_split_batch")
+
+
+def shamir_combine(indices, values, threshold: int, secrets_out, ok, stream=None) -> None:
+    """Shamir::combine for a batch (Shamir.cpp:152-163): indices uint8 [n,threshold], values uint8
+    [n,threshold,32] (each record's first `threshold` shares, in the caller's order); secrets_out
+    uint8 [n,32] (usable as a later batch's keys on the same stream); ok uint8 [n]: 0 and a zero
+    secret when two of a record's indices are equal."""
+    n = int(ok.numel())
+    _check(lib().enet_shamir_combine_batch(n, int(threshold), _ptr(indices), _ptr(values), _ptr(secrets_out),
+                                           _ptr(ok), _stream(stream)), "enet_shamir_combine_batch")
 
 
 def chunk_counter(chunk_id: bytes) -> int:

@@ -548,7 +548,7 @@ uint32_t choose_lanes(uint32_t n, uint64_t total_bytes, uint32_t max_len) {
 
 extern "C" {
 
-uint32_t enet_abi_version(void) { return (1u << 16) | 2u; }
+uint32_t enet_abi_version(void) { return (1u << 16) | 3u; }
 
 const char* enet_last_error(void) { return g_last_error.c_str(); }
 
@@ -885,6 +885,33 @@ int enet_session_key_batch(uint32_t n, const uint8_t* secrets, const uint64_t* c
     return hip_status(enet::launch_session_keys(n, secrets, counters, ticks, keys_out,
                                                 (hipStream_t)stream),
                       "session_key launch");
+}
+
+int enet_shamir_split_batch(uint32_t n, const uint8_t* secrets, const uint8_t* coeffs, uint32_t threshold,
+                            uint32_t share_count, uint8_t* shares, void* stream) {
+    if (threshold == 0 || threshold > share_count || share_count > 255)
+        return fail(ENET_EINVAL, "shamir_split: need 1 <= threshold <= share_count <= 255");
+    if (n == 0) return ENET_OK;
+    if (!secrets || !shares || (!coeffs && threshold > 1))
+        return fail(ENET_EINVAL, "shamir_split: NULL secrets, shares or coeffs");
+    if (!aligned4(secrets) || !aligned4(shares) || !aligned4(coeffs))
+        return fail(ENET_EINVAL, "shamir_split: secrets, coeffs and shares must be 4-byte aligned");
+    return hip_status(enet::launch_shamir_split(n, secrets, coeffs, threshold, share_count, shares,
+                                                (hipStream_t)stream),
+                      "shamir_split launch");
+}
+
+int enet_shamir_combine_batch(uint32_t n, uint32_t threshold, const uint8_t* indices, const uint8_t* values,
+                              uint8_t* secrets_out, uint8_t* ok, void* stream) {
+    if (threshold == 0 || threshold > 255) return fail(ENET_EINVAL, "shamir_combine: need 1 <= threshold <= 255");
+    if (n == 0) return ENET_OK;
+    if (!indices || !values || !secrets_out || !ok)
+        return fail(ENET_EINVAL, "shamir_combine: NULL indices, values, secrets_out or ok");
+    if (!aligned4(values) || !aligned4(secrets_out))
+        return fail(ENET_EINVAL, "shamir_combine: values and secrets_out must be 4-byte aligned");
+    return hip_status(enet::launch_shamir_combine(n, threshold, indices, values, secrets_out, ok,
+                                                  (hipStream_t)stream),
+                      "shamir_combine launch");
 }
 
 }  // extern "C"

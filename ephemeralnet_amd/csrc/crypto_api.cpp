@@ -993,6 +993,226 @@ std::vector<std::vector<std::uint8_t>> chunk_fetch(std::span<const Key> keys, st
     return res;
 }
 
+// ---- Shamir key shares (enet_shamir_*_batch) and the store / fetch steps that carry them
+namespace {
+// n random bytes: a ChaCha20 keystream under a key from std::random_device (fill_random_bytes),
+// one key per call -- std::random_device itself costs a system call or an RDRAND per 4 bytes
+std::vector<std::uint8_t> random_stream(std::size_t n) {
+    std::vector<std::uint8_t> out(n, 0);
+    std::uint8_t key[32];
+    const std::uint8_t nonce[12] = {};
+    fill_random_bytes(key);
+    enet_host_chacha20_xor(key, nonce, 0, out.data(), out.data(), n);
+    return out;
+}
+
+void check_split_args(std::uint8_t threshold, std::uint8_t share_count, const char* what) {
+    if (threshold == 0 || share_count == 0 || threshold > share_count)
+        throw std::invalid_argument(std::string("enet batch::") + what + ": need 1 <= threshold <= share_count");
+}
+
+// indices [n][t] behind values [n][t][32] in one buffer (values first: they need the alignment)
+std::vector<std::uint8_t> pack_shares(std::span<const std::vector<ShamirShare>> shares, std::uint8_t threshold,
+                                      const char* what) {
+    const std::size_t n = shares.size(), t = threshold;
+    if (t == 0) throw std::invalid_argument(std::string("enet batch::") + what + ": threshold is 0");
+    std::vector<std::uint8_t> buf(33 * n * t);
+    for (std::size_t i = 0; i < n; ++i) {
+        if (shares[i].size() < t)
+            throw std::invalid_argument(std::string("enet batch::") + what + ": a record has fewer shares than threshold");
+        for (std::size_t k = 0; k < t; ++k) {
+            std::memcpy(buf.data() + 32 * (i * t + k), shares[i][k].value.data(), 32);
+            buf[32 * n * t + i * t + k] = shares[i][k].index;
+        }
+    }
+    return buf;
+}
+
+std::vector<std::vector<ShamirShare>> unpack_shares(const std::vector<std::uint8_t>& flat, std::size_t n,
+                                                    std::size_t share_count) {
+    std::vector<std::vector<ShamirShare>> res(n, std::vector<ShamirShare>(share_count));
+    for (std::size_t i = 0; i < n; ++i)
+        for (std::size_t j = 0; j < share_count; ++j) {
+            res[i][j].index = static_cast<std::uint8_t>(j + 1);
+            std::memcpy(res[i][j].value.data(), flat.data() + 32 * (i * share_count + j), 32);
+        }
+    return res;
+}
+
+void check_count(std::size_t n, const char* what) {
+    if (n > 0xFFFFFFFFull) throw std::invalid_argument(std::string("enet batch::") + what + ": too many records");
+}
+
+// device memory also for a small batch (Staging serves small buffers from host-resident staging)
+constexpr std::size_t kDeviceOnly = Staging::kZeroCopyMax + 1;
+}  // namespace
+
+std::vector<std::vector<ShamirShare>> shamir_split(std::span<const std::array<std::uint8_t, 32>> secrets,
+                                                   std::uint8_t threshold, std::uint8_t share_count) {
+    check_split_args(threshold, share_count, "shamir_split");
+    const std::size_t n = secrets.size(), t = threshold, sc = share_count;
+    check_count(n, "shamir_split");
+    if (n == 0) return {};
+    const std::vector<std::uint8_t> coeffs = random_stream(32 * n * (t - 1));
+    return staged([&](Staging& st) {
+        auto* dsec = (uint8_t*)st.get(S_KEYS, 32 * n);
+        auto* dco = t > 1 ? (uint8_t*)st.get(S_AUX, coeffs.size()) : nullptr;
+        auto* dsh = (uint8_t*)st.get(S_OUT, 32 * n * sc);
+        st.h2d(dsec, secrets.data(), 32 * n);
+        st.h2d(dco, coeffs.data(), coeffs.size());
+        enet_check(enet_shamir_split_batch((uint32_t)n, dsec, dco, threshold, share_count, dsh, st.s()), "shamir_split");
+        std::vector<std::uint8_t> flat(32 * n * sc);
+        st.d2h(flat.data(), dsh, flat.size());
+        st.sync();
+        return unpack_shares(flat, n, sc);
+    });
+}
+
+std::vector<std::array<std::uint8_t, 32>> shamir_combine(std::span<const std::vector<ShamirShare>> shares,
+                                                         std::uint8_t threshold, std::vector<std::uint8_t>& ok) {
+    const std::size_t n = shares.size(), t = threshold;
+    check_count(n, "shamir_combine");
+    const std::vector<std::uint8_t> packed = pack_shares(shares, threshold, "shamir_combine");
+    ok.assign(n, 0);
+    if (n == 0) return {};
+    return staged([&](Staging& st) {
+        auto* dsh = (uint8_t*)st.get(S_AUX, packed.size());
+        auto* dsec = (uint8_t*)st.get(S_KEYS, 32 * n);
+        auto* dok = (uint8_t*)st.get(S_OK, n);
+        st.h2d(dsh, packed.data(), packed.size());
+        enet_check(enet_shamir_combine_batch((uint32_t)n, threshold, dsh + 32 * n * t, dsh, dsec, dok, st.s()),
+                   "shamir_combine");
+        std::vector<std::array<std::uint8_t, 32>> res(n);
+        st.d2h(res.data(), dsec, 32 * n);
+        st.d2h(ok.data(), dok, n);
+        st.sync();
+        return res;
+    });
+}
+
+namespace {
+// the records descriptor of a chunk batch whose arenas share one offsets array
+enet_records chunk_records(std::size_t n, const Packed& p, const uint64_t* doff, const uint8_t* din, uint8_t* dout,
+                           const uint8_t* dkeys, const uint8_t* dnonces, const char* what) {
+    uint64_t longest = 0;
+    for (std::size_t i = 0; i < n; ++i) longest = std::max(longest, p.off[i + 1] - p.off[i]);
+    if (longest > 0xFFFFFFFFull) throw std::invalid_argument(std::string("enet batch::") + what + ": chunk too long");
+    enet_records r{};
+    r.count = (uint32_t)n;
+    r.in_offsets = doff;
+    r.out_offsets = doff;
+    r.in = din;
+    r.out = dout;
+    r.keys = dkeys;
+    r.key_stride = 32;
+    r.nonces = dnonces;
+    r.total_bytes_hint = p.off[n];
+    r.max_len_hint = (uint32_t)longest;
+    return r;
+}
+}  // namespace
+
+std::vector<SharedChunk> chunk_store_shared(std::span<const Nonce> nonces,
+                                            std::span<const std::span<const std::uint8_t>> chunks,
+                                            std::span<const ChunkId> chunk_ids, std::uint8_t threshold,
+                                            std::uint8_t share_count) {
+    check_split_args(threshold, share_count, "chunk_store_shared");
+    const std::size_t n = chunks.size(), t = threshold, sc = share_count;
+    if (nonces.size() != n || (!chunk_ids.empty() && chunk_ids.size() != n))
+        throw std::invalid_argument("enet batch::chunk_store_shared: size mismatch");
+    check_count(n, "chunk_store_shared");
+    if (n == 0) return {};
+    // keys [n][32], then the coefficient rows [n][t-1][32]
+    const std::vector<std::uint8_t> rnd = random_stream(32 * n * t);
+    const Packed in = pack(chunks);
+    return staged([&](Staging& st) {
+        const std::size_t bytes = in.arena.size();
+        auto* din = (uint8_t*)st.get(S_IN, bytes);
+        auto* dout = (uint8_t*)st.get(S_OUT, bytes);
+        auto* doff = (uint64_t*)st.get(S_INOFF, 8 * (n + 1));
+        auto* dkeys = (uint8_t*)st.get(S_KEYS, 32 * n);
+        auto* dco = t > 1 ? (uint8_t*)st.get(S_AUX, 32 * n * (t - 1)) : nullptr;
+        auto* dnon = (uint8_t*)st.get(S_NONCES, 12 * n);
+        auto* dids = chunk_ids.empty() ? nullptr : (uint8_t*)st.get(S_CTR, 32 * n);
+        auto* dhash = (uint8_t*)st.get(S_TAGS, 32 * n);
+        auto* dsh = (uint8_t*)st.get(S_OK, 32 * n * sc);
+        st.h2d(din, in.arena.data(), bytes);
+        st.h2d(doff, in.off.data(), 8 * (n + 1));
+        st.h2d(dkeys, rnd.data(), 32 * n);
+        st.h2d(dco, rnd.data() + 32 * n, 32 * n * (t - 1));
+        st.h2d(dnon, nonce_bytes(nonces), 12 * n);
+        if (dids) st.h2d(dids, chunk_ids.data()->data(), 32 * n);
+        const enet_records r = chunk_records(n, in, doff, din, dout, dkeys, dnon, "chunk_store_shared");
+        enet_check(enet_chunk_store_batch(&r, dids, dhash, st.s()), "chunk_store");
+        enet_check(enet_shamir_split_batch((uint32_t)n, dkeys, dco, threshold, share_count, dsh, st.s()),
+                   "shamir_split");
+        std::vector<std::uint8_t> data(bytes), hh(32 * n), flat(32 * n * sc);
+        st.d2h(data.data(), dout, bytes);
+        st.d2h(hh.data(), dhash, 32 * n);
+        st.d2h(flat.data(), dsh, flat.size());
+        st.sync();
+        auto shares = unpack_shares(flat, n, sc);
+        std::vector<SharedChunk> res(n);
+        for (std::size_t i = 0; i < n; ++i) {
+            res[i].chunk.data.assign(data.begin() + in.off[i], data.begin() + in.off[i + 1]);
+            std::memcpy(res[i].chunk.chunk_hash.data(), hh.data() + 32 * i, 32);
+            res[i].shares = std::move(shares[i]);
+        }
+        return res;
+    });
+}
+
+std::vector<std::vector<std::uint8_t>> chunk_fetch_shared(std::span<const std::vector<ShamirShare>> shares,
+                                                          std::uint8_t threshold, std::span<const Nonce> nonces,
+                                                          std::span<const ChunkId> chunk_ids,
+                                                          std::span<const std::span<const std::uint8_t>> ciphertexts,
+                                                          std::span<const std::array<std::uint8_t, 32>> chunk_hashes,
+                                                          std::vector<std::uint8_t>& ok) {
+    const std::size_t n = ciphertexts.size(), t = threshold;
+    if (shares.size() != n || nonces.size() != n || chunk_ids.size() != n || chunk_hashes.size() != n)
+        throw std::invalid_argument("enet batch::chunk_fetch_shared: size mismatch");
+    check_count(n, "chunk_fetch_shared");
+    const std::vector<std::uint8_t> packed = pack_shares(shares, threshold, "chunk_fetch_shared");
+    ok.assign(n, 0);
+    if (n == 0) return {};
+    const Packed in = pack(ciphertexts);
+    return staged([&](Staging& st) {
+        const std::size_t bytes = in.arena.size(), okpad = (n + 3) & ~std::size_t(3);
+        auto* din = (uint8_t*)st.get(S_IN, bytes);
+        auto* dout = (uint8_t*)st.get(S_OUT, bytes);
+        auto* doff = (uint64_t*)st.get(S_INOFF, 8 * (n + 1));
+        auto* dsh = (uint8_t*)st.get(S_AUX, packed.size());
+        auto* dkeys = (uint8_t*)st.get(S_KEYS, std::max(32 * n, kDeviceOnly));
+        auto* dnon = (uint8_t*)st.get(S_NONCES, 12 * n);
+        auto* dids = (uint8_t*)st.get(S_CTR, 32 * n);
+        auto* dhash = (uint8_t*)st.get(S_TAGS, 32 * n);
+        auto* dok = (uint8_t*)st.get(S_OK, 2 * okpad);  // the combine's verdicts, then the fetch's
+        st.h2d(din, in.arena.data(), bytes);
+        st.h2d(doff, in.off.data(), 8 * (n + 1));
+        st.h2d(dsh, packed.data(), packed.size());
+        st.h2d(dnon, nonce_bytes(nonces), 12 * n);
+        st.h2d(dids, chunk_ids.data()->data(), 32 * n);
+        st.h2d(dhash, chunk_hashes.data()->data(), 32 * n);
+        enet_check(enet_shamir_combine_batch((uint32_t)n, threshold, dsh + 32 * n * t, dsh, dkeys, dok, st.s()),
+                   "shamir_combine");
+        const enet_records r = chunk_records(n, in, doff, din, dout, dkeys, dnon, "chunk_fetch_shared");
+        enet_check(enet_chunk_fetch_batch(&r, dids, dhash, dok + okpad, st.s()), "chunk_fetch");
+        std::vector<std::uint8_t> data(bytes), oks(2 * okpad);
+        st.d2h(data.data(), dout, bytes);
+        st.d2h(oks.data(), dok, oks.size());
+        st.sync();
+        std::vector<std::vector<std::uint8_t>> res(n);
+        for (std::size_t i = 0; i < n; ++i) {
+            ok[i] = oks[i] & oks[okpad + i];
+            res[i].assign(data.begin() + in.off[i], data.begin() + in.off[i + 1]);
+            // a failed combine leaves the all-zero key, whose plaintext can only pass the hash check
+            // by being the real one; it is withheld all the same
+            if (!ok[i]) std::fill(res[i].begin(), res[i].end(), std::uint8_t{0});
+        }
+        return res;
+    });
+}
+
 void wire_seal(std::span<const std::array<std::uint8_t, 32>> session_keys, std::span<const Nonce> nonces,
                std::span<const std::span<const std::uint8_t>> messages, std::vector<std::vector<std::uint8_t>>& frames) {
     const size_t n = messages.size();

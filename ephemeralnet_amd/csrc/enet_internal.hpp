@@ -156,6 +156,12 @@ hipError_t launch_hmac_midstates(uint32_t n, const uint8_t* keys, uint32_t* mid,
 hipError_t launch_session_keys(uint32_t n, const uint8_t* secrets, const uint64_t* counters,
                                const int64_t* ticks, uint8_t* out, hipStream_t s);
 
+// Shamir split / combine of 32-byte secrets over GF(2^8)/0x11D (shamir.hip); 1 <= threshold <=
+// share_count <= 255, the 32-byte-row buffers 4-byte aligned (checked by the C ABI)
+hipError_t launch_shamir_split(uint32_t n, const uint8_t* secrets, const uint8_t* coeffs, uint32_t threshold,
+                               uint32_t share_count, uint8_t* shares, hipStream_t s);
+hipError_t launch_shamir_combine(uint32_t n, uint32_t threshold, const uint8_t* indices, const uint8_t* values,
+                                 uint8_t* secrets_out, uint8_t* ok, hipStream_t s);
 
 // ---- sequence-parallel path for long records (segments.hip)
 // A claimed record's entry; entries are sorted by tile_base (claimed by CAS on one packed word).

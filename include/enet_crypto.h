@@ -214,6 +214,37 @@ ENET_API int enet_pow_check_batch(uint32_t n, const uint8_t* prefixes,
 ENET_API int enet_session_key_batch(uint32_t n, const uint8_t* secrets, const uint64_t* counters,
                                     const int64_t* ticks, uint8_t* keys_out, void* stream);
 
+/* ---- Shamir key shares (reference: Shamir::split / Shamir::combine, src/crypto/Shamir.cpp:114-163,
+ *      include/ephemeralnet/crypto/Shamir.hpp:12-25): the 32-byte chunk key is split when a chunk
+ *      is stored (Node::store_chunk, src/core/Node.cpp:1428) and combined before it is decrypted
+ *      (Node::receive_chunk / fetch_chunk, :1632-1642, :1804-1813; src/main.cpp:816-825).  Byte by
+ *      byte over GF(2^8) with the reference's field -- reduction polynomial 0x11D, generator 2
+ *      (Shamir.cpp:10-26), not the AES field -- multiplied without tables (the reference indexes
+ *      log / exp tables by key bytes, :41-49).  `threshold` is uniform per call (the node's
+ *      config value); callers group by threshold.
+ * split:   shares [n][share_count][32], share j of record i has index j + 1 and is the record's
+ *          polynomial at x = j + 1 (evaluate_polynomial, :68-80): constant term secrets[i] ([n][32]),
+ *          degree-d coefficient (d = 1 .. threshold-1) the 32 caller-supplied random bytes at
+ *          coeffs + ((i * (threshold-1) + d-1) * 32) -- the reference draws them from
+ *          std::random_device (:127,141).  coeffs may be NULL when threshold == 1.
+ * combine: Lagrange interpolation at 0 (interpolate, :82-110) over the FIRST `threshold` shares of
+ *          each record in the caller's order, as the reference takes them (:161): indices
+ *          [n][threshold], values [n][threshold][32]; secrets_out [n][32] is directly usable as
+ *          enet_records.keys (key_stride 32) by a later call on the same stream; ok [n].  An index
+ *          of 0 is legal (the share at x = 0 is the secret).  Two equal indices among a record's
+ *          first `threshold` give ok[i] = 0 and 32 zero bytes (fail closed, as every open here).
+ *          That is deliberately stricter than the reference in one corner: it throws "division by
+ *          zero" there (:54-56) only if a value byte it would multiply is non-zero (:90-92), and
+ *          returns a secret for duplicate all-zero shares.
+ * secrets, coeffs, shares, values and secrets_out must be 4-byte aligned.  ENET_EINVAL (nothing
+ * launched) unless 1 <= threshold <= share_count <= 255 (combine: threshold <= 255). */
+ENET_API int enet_shamir_split_batch(uint32_t n, const uint8_t* secrets, const uint8_t* coeffs,
+                                     uint32_t threshold, uint32_t share_count, uint8_t* shares,
+                                     void* stream);
+ENET_API int enet_shamir_combine_batch(uint32_t n, uint32_t threshold, const uint8_t* indices,
+                                       const uint8_t* values, uint8_t* secrets_out, uint8_t* ok,
+                                       void* stream);
+
 /* ---- host-resident pipeline
  * The reference's crypto path starts and ends in host memory (socket / relay buffers,
  * SessionManager.cpp:362-387 and 815-822; chunk files, Node.cpp:1414-1417 and 1641-1655).  These

@@ -15,6 +15,7 @@
 
 #include "ephemeralnet/crypto/CryptoTypes.hpp"
 #include "ephemeralnet/crypto/ChaCha20.hpp"
+#include "ephemeralnet/crypto/Shamir.hpp"
 
 namespace ephemeralnet::crypto::batch {
 
@@ -104,6 +105,43 @@ ENET_CXX_API std::vector<StoredChunk> chunk_store(std::span<const Key> keys,
 ENET_CXX_API std::vector<std::vector<std::uint8_t>> chunk_fetch(
     std::span<const Key> keys, std::span<const Nonce> nonces, std::span<const ChunkId> chunk_ids,
     std::span<const std::span<const std::uint8_t>> ciphertexts,
+    std::span<const std::array<std::uint8_t, 32>> chunk_hashes, std::vector<std::uint8_t>& ok);
+
+// Shamir key shares for many 32-byte secrets (Shamir::split / Shamir::combine,
+// src/crypto/Shamir.cpp:114-163), one device pass per call (enet_shamir_*_batch).
+// shamir_split: result[i] = the share_count shares of secrets[i], indices 1 .. share_count, any
+// `threshold` of which give the secret back.  The polynomial coefficients are a ChaCha20 keystream
+// under a key drawn from std::random_device per call (the reference draws every coefficient byte
+// from std::random_device, :127,141).  std::invalid_argument as Shamir::split.
+ENET_CXX_API std::vector<std::vector<ShamirShare>> shamir_split(
+    std::span<const std::array<std::uint8_t, 32>> secrets, std::uint8_t threshold, std::uint8_t share_count);
+// shamir_combine: result[i] from the first `threshold` entries of shares[i], in their order.
+// std::invalid_argument when threshold is 0 or a record has fewer shares.  ok[i] = 0 and a zero
+// result when two of those entries have the same index (the reference throws there unless the
+// values are zero; a batch fails closed per record instead).
+ENET_CXX_API std::vector<std::array<std::uint8_t, 32>> shamir_combine(
+    std::span<const std::vector<ShamirShare>> shares, std::uint8_t threshold, std::vector<std::uint8_t>& ok);
+
+// The node's store step with the key sharing included (Node::store_chunk, Node.cpp:1414-1428):
+// a fresh key per chunk (CryptoManager::generate_key; here a ChaCha20 keystream under a
+// std::random_device key), chunk_store under those keys and the split of the keys, on one stream.
+// The keys themselves are not returned: any `threshold` of a chunk's shares are its key.
+struct SharedChunk {
+    StoredChunk chunk;
+    std::vector<ShamirShare> shares;
+};
+ENET_CXX_API std::vector<SharedChunk> chunk_store_shared(std::span<const Nonce> nonces,
+                                                         std::span<const std::span<const std::uint8_t>> chunks,
+                                                         std::span<const ChunkId> chunk_ids, std::uint8_t threshold,
+                                                         std::uint8_t share_count);
+// ... and the fetch step (Node::receive_chunk / fetch_chunk, Node.cpp:1632-1655): the first
+// `threshold` shares of every chunk are combined on the device and chunk_fetch runs on the same
+// stream with the combined keys where they lie -- no key crosses to the host.  ok[i] = 1 only
+// when the shares combined (no duplicate index) AND the plaintext's SHA-256 equals
+// chunk_hashes[i]; failed entries come back zeroed.
+ENET_CXX_API std::vector<std::vector<std::uint8_t>> chunk_fetch_shared(
+    std::span<const std::vector<ShamirShare>> shares, std::uint8_t threshold, std::span<const Nonce> nonces,
+    std::span<const ChunkId> chunk_ids, std::span<const std::span<const std::uint8_t>> ciphertexts,
     std::span<const std::array<std::uint8_t, 32>> chunk_hashes, std::vector<std::uint8_t>& ok);
 
 // Whole wire frames nonce(12) || BE32(|body|) || ChaCha20_{K,N,0}(m || HMAC_K(m)) -- what
