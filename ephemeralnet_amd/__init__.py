@@ -59,7 +59,7 @@ EXPORTS = [
     "enet_aead_hmac_seal_batch",
     "enet_aead_hmac_open_batch", "enet_chunk_counter",
     "enet_lanes_per_record", "enet_set_lanes_per_record", "enet_set_staging", "enet_set_duplex_split",
-    "enet_set_seg_min", "enet_seg_batches", "enet_set_host_hash_min", "enet_host_hash_batches", "enet_last_error",
+    "enet_set_seg_min", "enet_seg_batches", "enet_record_route_counts", "enet_set_host_hash_min", "enet_host_hash_batches", "enet_last_error",
     "enet_abi_version", "enet_pipeline_create", "enet_pipeline_destroy",
     "enet_pipeline_chacha20_xor", "enet_pipeline_aead_seal", "enet_pipeline_aead_open",
     "enet_pipeline_aead_hmac_seal", "enet_pipeline_aead_hmac_open", "enet_pipeline_wire_seal",
@@ -160,6 +160,8 @@ def lib() -> C.CDLL:
         L.enet_set_duplex_split.argtypes = [C.c_int]
         L.enet_set_seg_min.argtypes = [C.c_int64]
         L.enet_seg_batches.restype = C.c_uint64
+        L.enet_record_route_counts.argtypes = [C.POINTER(C.c_uint64)]
+        L.enet_record_route_counts.restype = None
         L.enet_set_host_hash_min.argtypes = [C.c_int64]
         L.enet_host_hash_batches.restype = C.c_uint64
         L.enet_last_error.restype = C.c_char_p
@@ -274,6 +276,17 @@ def set_seg_min(nbytes: int) -> None:
 
 def seg_batches() -> int:
     return int(lib().enet_seg_batches())
+
+
+ROUTE_KINDS = ("PerLane", "RunStaged", "LineStaged", "Lockstep", "Stream")
+
+
+def record_route_counts() -> dict:
+    """enet_record_route_counts: records handed so far, in this process, to launches of each record
+    kernel kind (csrc/record_route.hpp RecordKind)."""
+    out = (C.c_uint64 * len(ROUTE_KINDS))()
+    lib().enet_record_route_counts(out)
+    return dict(zip(ROUTE_KINDS, (int(v) for v in out)))
 
 
 SEG_MIN = 256 << 10

@@ -548,7 +548,7 @@ uint32_t choose_lanes(uint32_t n, uint64_t total_bytes, uint32_t max_len) {
 
 extern "C" {
 
-uint32_t enet_abi_version(void) { return (1u << 16) | 3u; }
+uint32_t enet_abi_version(void) { return (1u << 16) | 4u; }
 
 const char* enet_last_error(void) { return g_last_error.c_str(); }
 
@@ -581,6 +581,10 @@ int enet_set_seg_min(int64_t bytes) {
 }
 
 uint64_t enet_seg_batches(void) { return enet::seg_batches(); }
+
+void enet_record_route_counts(uint64_t out[5]) {
+    if (out) enet::record_route_counts(out);
+}
 
 int enet_set_lanes_per_record(uint32_t lanes) {
     if (lanes != 0 && lanes != 1 && lanes != 2 && lanes != 4 && lanes != 8 && lanes != 16)

@@ -59,8 +59,10 @@ struct RecParams {
 
 // lanes: 1, 2, 4, 8 or 16 lanes per record.
 hipError_t launch_records(int mode, const RecParams& p, uint32_t lanes, hipStream_t s);
-// The streaming kernel (stream.hip): whole 512-thread workgroups of a uniform batch.
-bool stream_eligible(const RecParams& p, uint32_t lanes);
+// records handed to launches of each kind so far (record_route.hpp RecordKind order; records.hip)
+void record_route_counts(uint64_t out[5]);
+// The streaming kernel (stream.hip): whole 512-thread workgroups of a uniform batch
+// (record_route.hpp decides which batches).
 hipError_t launch_stream(int mode, const RecParams& p, uint32_t lanes, uint32_t blocks, hipStream_t s);
 
 struct ShaParams {

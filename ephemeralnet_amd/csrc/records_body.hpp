@@ -529,7 +529,11 @@ __device__ __forceinline__ void records_body(const RecParams& p) {
             reinterpret_cast<const uint8_t*>(uniform_u64(reinterpret_cast<uintptr_t>(ibase - (ib & 127u))));
         uint8_t* oal = reinterpret_cast<uint8_t*>(uniform_u64(reinterpret_cast<uintptr_t>(obase - (ib & 127u))));
         uint32_t roff[8];  // line 0 of owner o
-        uint32_t rgeo[8];  // d | lines << 8 | end-bytes-in-last-line << 16
+        // d | lines << 8 (a record of L < 2^24 bytes spans up to 2^17 + 1 lines: an 8-bit field
+        // dropped the first and last line of every record of 256 lines or more,
+        // tests/test_gpu_uniform_matrix.py::test_line_staged_records_of_256_lines); the bytes the
+        // record has in its last line follow from d and L
+        uint32_t rgeo[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const uint32_t o = 8u * i + rq;
@@ -537,8 +541,7 @@ __device__ __forceinline__ void records_body(const RecParams& p) {
             const uint32_t d = (ib + g * Lu) & 127u;
             roff[i] = g * Lu + (ib & 127u) - d;
             const uint32_t nl = (d + Lu + 127u) >> 7;
-            const uint32_t e = ((d + Lu - 1u) & 127u) + 1u;
-            rgeo[i] = d | (nl << 8) | (e << 16);
+            rgeo[i] = d | (nl << 8);
         }
         uint32_t pf[32];
         auto fetch = [&](uint32_t t) {  // line t of every role owner -> pf (only lines it has)
@@ -552,7 +555,7 @@ __device__ __forceinline__ void records_body(const RecParams& p) {
             }
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                if (t < ((rgeo[i] >> 8) & 0xffu)) {
+                if (t < (rgeo[i] >> 8)) {
                     const uint4 v = *reinterpret_cast<const uint4*>(ial + (roff[i] + 128u * t + 16u * rc));
                     pf[4 * i] = v.x; pf[4 * i + 1] = v.y; pf[4 * i + 2] = v.z; pf[4 * i + 3] = v.w;
                 }
@@ -574,7 +577,7 @@ __device__ __forceinline__ void records_body(const RecParams& p) {
         auto store_line = [&](uint32_t t) {  // ring slot t % 2 -> line t, this record's bytes only
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                const uint32_t d = rgeo[i] & 0xffu, nl = (rgeo[i] >> 8) & 0xffu, e = rgeo[i] >> 16;
+                const uint32_t d = rgeo[i] & 0xffu, nl = rgeo[i] >> 8, e = ((d + Lu - 1u) & 127u) + 1u;
                 if (t >= nl) continue;
                 const uint32_t lo = t == 0 ? d : 0u, hi = t + 1 == nl ? e : 128u;
                 const uint32_t c0 = 16u * rc;

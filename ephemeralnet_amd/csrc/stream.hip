@@ -33,6 +33,7 @@
 //
 // Reference behaviour: ChaCha20::apply (src/crypto/ChaCha20.cpp:98-121, u32 counter wrap :110)
 // for MODE_XOR; RFC 8439 AEAD (no reference implementation) for seal / open.
+#include "record_route.hpp"
 #include "stream_common.hpp"
 
 namespace enet {
@@ -474,11 +475,8 @@ static hipError_t launch_stream_mode(const RecParams& p, uint32_t lanes, uint32_
     return hipGetLastError();
 }
 
-bool stream_eligible(const RecParams& p, uint32_t lanes) {
-    const uint64_t L = p.uniform_len;
-    return (p.stream & 1) && L != 0 && p.order == nullptr && L % (128ull * lanes) == 0 &&
-           L * (uint64_t)p.n <= 0xFFFFFFFFull && p.n >= kStreamLanes / lanes;
-}
+// which batches come here: record_route.hpp choose_record_route (RecordKind::Stream)
+static_assert(kRouteWideWG == kStreamLanes, "record_route.hpp and the streaming kernel disagree on the workgroup");
 
 hipError_t launch_stream(int mode, const RecParams& p, uint32_t lanes, uint32_t blocks, hipStream_t s) {
     switch (mode) {

@@ -420,6 +420,12 @@ ENET_API int enet_set_host_hash_min(int64_t bytes);
 ENET_API uint64_t enet_host_hash_batches(void);
 /* Batches that have taken the sequence-parallel path in this process (tests / tuning). */
 ENET_API uint64_t enet_seg_batches(void);
+/* Which record kernel the batches of this process ran on: out[k] = records handed so far to
+ * launches of kind k -- 0 per-lane, 1 run-staged (256-thread workgroups), 2 line-staged, 3 lockstep
+ * run-staged (512-thread workgroups), 4 streaming.  A uniform batch counts its whole workgroups
+ * under the staged / streaming kind and its remaining records under 0.  Cumulative, relaxed
+ * atomics (tests / tuning). */
+ENET_API void enet_record_route_counts(uint64_t out[5]);
 /* Staging of uniform-length batches (all records the same length): 1 = register prefetch + LDS
  * transposition (default; records that are not 128-byte aligned and get one lane each are staged
  * as whole aligned 128-byte lines; the rest in lockstep 512-thread workgroups), 4 = 1 without the

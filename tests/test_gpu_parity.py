@@ -479,7 +479,7 @@ def test_wire_frames_random_vs_oracle(enet, lanes):
 # ------------------------------------------------------------------------------ uniform (COOP)
 @pytest.mark.parametrize("staging", [1, 0, 4, 5])
 @pytest.mark.parametrize("L,n,lanes", [(1500, 1000, 1), (1500, 517, 2), (4096, 300, 2),
-                                       (4096, 129, 4), (65536, 40, 8), (65536, 33, 16),
+                                       (4096, 129, 4), (65536, 72, 8), (65536, 33, 16),
                                        (640, 700, 1), (127, 300, 1), (64, 260, 1), (0, 10, 1),
                                        (1504, 300, 1), (1472, 300, 1), (1400, 300, 1),
                                        (200, 300, 1), (100, 260, 1), (80, 300, 1), (31, 300, 1),
@@ -660,7 +660,8 @@ def test_aead_uniform_aad_vs_oracle(enet, L, n, lanes, staging):
 
 # ------------------------------------------------------------------------------ lying hints
 @pytest.mark.parametrize("staging", [1, 4, 5])
-@pytest.mark.parametrize("L,lanes", [(4096, 2), (4096, 1), (1500, 1), (65536, 16), (2048, 4)])
+@pytest.mark.parametrize("L,lanes", [(4096, 2), (4096, 1), (1500, 1), (65536, 16), (2048, 4),
+                                      (65536, 8)])
 def test_lying_hints_give_correct_bytes(enet, L, lanes, staging):
     """The hints say uniform (total == n * max_len_hint) but two records are 64 bytes shorter /
     longer than max_len_hint: the staged and streaming paths address records at in_off[0] + g L,

@@ -153,7 +153,7 @@ def test_shamir_abi_rejects_bad_arguments_without_gpu(lib_path):
     and misaligned 32-byte-row buffers return ENET_EINVAL; n == 0 is a no-op."""
     import ephemeralnet_amd as E
     L = E.lib()
-    assert L.enet_abi_version() == (1 << 16) | 3
+    assert L.enet_abi_version() == (1 << 16) | 4
     raw = (C.c_uint8 * 4096)()
     base = (C.addressof(raw) + 15) & ~15     # 16-byte aligned host memory: never dereferenced
     a, b, c, d = base, base + 1024, base + 2048, base + 3072
