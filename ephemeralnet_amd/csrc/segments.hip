@@ -7,7 +7,9 @@
 // to 1 MiB (src/network/SessionManager.cpp:87).  On the record engine one such record got 16
 // lanes: a lone 32 MiB AEAD record was 32 768 serial ChaCha20 blocks per lane.
 //
-// Three steps on the caller's stream:
+// A batch whose hints say every record is long takes ONE launch: seg_uniform_xor_kernel (ChaCha20)
+// or seg_uniform_aead_kernel (RFC 8439 seal / open), described where they stand below.  Every other
+// batch with long records (long and short mixed) takes three steps on the caller's stream:
 //   1. seg_plan_kernel: every record >= the threshold CLAIMS a contiguous range of tile indices
 //      (one 64-bit CAS on a packed count|tiles word, so entries come out sorted by tile base) and
 //      writes its entry -- for the AEAD also the one-time Poly1305 key and the power table
@@ -86,8 +88,9 @@ __device__ __forceinline__ void psquare(uint32_t h[5]) {
     c = h[0] >> 26; h[0] &= M26; h[1] += c;
 }
 
-// Sum of the workgroup's 256 accumulators (limbs < 2^27) into thread 0's l (limbs < 2^27)
-__device__ __forceinline__ void wg_sum(uint32_t l[5], uint32_t* red /* [4][5] shared */) {
+// Sum of the wave's 64 accumulators (limbs < 2^27) into every lane's l (limbs < 2^27): a carry
+// after 16 summands keeps the limbs inside 32 bits
+__device__ __forceinline__ void wave_sum(uint32_t l[5]) {
 #pragma unroll
     for (int off = 1; off <= 8; off <<= 1) {
 #pragma unroll
@@ -100,6 +103,11 @@ __device__ __forceinline__ void wg_sum(uint32_t l[5], uint32_t* red /* [4][5] sh
         for (int i = 0; i < 5; ++i) l[i] += __shfl_xor(l[i], off);
     }
     pcarry(l);
+}
+
+// Sum of the workgroup's 256 accumulators (limbs < 2^27) into thread 0's l (limbs < 2^27)
+__device__ __forceinline__ void wg_sum(uint32_t l[5], uint32_t* red /* [4][5] shared */) {
+    wave_sum(l);
     const uint32_t w = threadIdx.x >> 6;
     if ((threadIdx.x & 63u) == 0) {
 #pragma unroll
@@ -117,6 +125,69 @@ __device__ __forceinline__ void wg_sum(uint32_t l[5], uint32_t* red /* [4][5] sh
 __device__ __forceinline__ uint32_t seg_counter(const SegParams& p, uint32_t rec) {
     if (p.mode != MODE_XOR) return 1u;  // RFC 8439 data counter
     return p.counters ? p.counters[(size_t)rec * (p.counter_stride ? p.counter_stride : 1u)] : 0u;
+}
+
+// Record rec's key and nonce into its ChaCha20 state
+__device__ __forceinline__ void seg_record_init(ChachaRecord& R, const SegParams& p, uint32_t rec) {
+    uint32_t kw[8], nw[3];
+    const uint32_t* kp = reinterpret_cast<const uint32_t*>(p.keys + (size_t)p.key_stride * rec);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) kw[i] = kp[i];
+    const uint32_t* np = reinterpret_cast<const uint32_t*>(p.nonces + 12ull * rec);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) nw[i] = np[i];
+    chacha_record_init(R, kw, nw);
+}
+
+// The record's tag from its Poly1305 sum h and the pad s: seal writes it; open compares it with
+// the given one, sets the verdict and returns the difference (0 = authentic)
+template <int MODE>
+__device__ __forceinline__ uint32_t seg_tag_finish(const uint32_t h[5], const uint32_t* s, const SegParams& p,
+                                                   uint32_t rec) {
+    uint32_t tag[4];
+    pfinish(h, s, tag);
+    if (MODE == MODE_SEAL) {
+        uint32_t* tp = reinterpret_cast<uint32_t*>(p.tag_out + 16ull * rec);
+        tp[0] = tag[0]; tp[1] = tag[1]; tp[2] = tag[2]; tp[3] = tag[3];
+        return 0;
+    }
+    const uint32_t* tp = reinterpret_cast<const uint32_t*>(p.tag_in + 16ull * rec);
+    const uint32_t diff = (tag[0] ^ tp[0]) | (tag[1] ^ tp[1]) | (tag[2] ^ tp[2]) | (tag[3] ^ tp[3]);
+    p.ok[rec] = diff == 0 ? 1 : 0;
+    return diff;
+}
+
+// Where one tile of a record and one of its 256 lanes lie: lane j owns blocks [c0, c1) of the
+// tile's [tb0, tb1), clipped to the record's L bytes; na / nct = Poly1305 blocks of the AAD / of
+// the ciphertext (0 in XOR mode, where the *_end fields are unused).
+struct TileGeom {
+    uint32_t nb, j;
+    uint32_t tb0, tb1, c0, c1;
+    bool whole;  // all 1024 blocks inside the record: uniform over the tile's lanes
+    // the tile holds the record's end
+    __device__ __forceinline__ bool last_tile() const { return tb1 == nb; }
+    // this lane holds the record's last block: it absorbs the length block
+    __device__ __forceinline__ bool has_last() const { return (c1 == nb && c1 > c0) || (nb == 0 && j == 0); }
+    // positions (Poly1305 block index + 1) where this lane's and the tile's runs end
+    // (na / nct = Poly1305 blocks of the AAD / of the ciphertext)
+    __device__ __forceinline__ uint32_t lane_end(uint32_t na, uint32_t nct) const {
+        return na + min(4u * c1, nct) + (has_last() ? 1u : 0u);
+    }
+    __device__ __forceinline__ uint32_t tile_end(uint32_t na, uint32_t nct) const {
+        return na + min(4u * tb1, nct) + (last_tile() ? 1u : 0u);
+    }
+};
+
+__device__ __forceinline__ TileGeom tile_geom(uint64_t L, uint32_t tile, uint32_t j) {
+    TileGeom g;
+    g.nb = (uint32_t)((L + 63) >> 6);
+    g.j = j;
+    g.tb0 = tile * kTileBlocks;
+    g.tb1 = min(g.tb0 + kTileBlocks, g.nb);
+    g.c0 = min(g.tb0 + kSegBPL * j, g.tb1);
+    g.c1 = min(g.c0 + kSegBPL, g.tb1);
+    g.whole = (uint64_t)(g.tb0 + kTileBlocks) * 64ull <= L;
+    return g;
 }
 
 // ---------------------------------------------------------------------------------- plan
@@ -159,15 +230,8 @@ __global__ __launch_bounds__(kSegThreads) void seg_plan_kernel(SegParams p) {
         e.arrived = 0;
         if (p.mode == MODE_XOR) continue;
         // AEAD: one-time key = block 0 (RFC 8439 2.6), AAD length, power table
-        uint32_t kw[8], nw[3];
-        const uint32_t* kp = reinterpret_cast<const uint32_t*>(p.keys + (size_t)p.key_stride * i);
-#pragma unroll
-        for (int t = 0; t < 8; ++t) kw[t] = kp[t];
-        const uint32_t* np = reinterpret_cast<const uint32_t*>(p.nonces + 12ull * i);
-#pragma unroll
-        for (int t = 0; t < 3; ++t) nw[t] = np[t];
         ChachaRecord R;
-        chacha_record_init(R, kw, nw);
+        seg_record_init(R, p, i);
         uint32_t otk[16];
         chacha_block(R, 0u, otk);
 #pragma unroll
@@ -187,6 +251,54 @@ __global__ __launch_bounds__(kSegThreads) void seg_plan_kernel(SegParams p) {
 #pragma unroll
             for (int t = 0; t < 5; ++t) e.pw[5 * k + t] = x[t];
             pmul(x, pmul_make(x));
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------- tile bodies
+// The record's AAD (aad_len bytes at ap, the last block zero-padded) into the Horner h
+__device__ __forceinline__ void poly_absorb_aad(uint32_t h[5], const PolyR32& PR, const uint8_t* ap, uint32_t aad_len) {
+    const uint32_t na = (aad_len + 15) >> 4;
+    for (uint32_t s = 0; s < na; ++s) {
+        const uint32_t cnt = min(16u, aad_len - 16u * s);
+        uint32_t w[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            uint32_t v = 0;
+#pragma unroll
+            for (int b = 0; b < 4; ++b)
+                if ((uint32_t)(4 * i + b) < cnt) v |= (uint32_t)ap[16 * s + 4 * i + b] << (8 * b);
+            w[i] = v;
+        }
+        poly32_block(h, PR, w[0], w[1], w[2], w[3], 1u);
+    }
+}
+
+// A ragged tile (the record's last, or all of a record shorter than a tile): lane by lane over its
+// blocks [c0, c1), the partial block masked; AEAD modes absorb the ciphertext into h.  (The
+// one-launch AEAD kernel keeps its own copies, one of them with write-through stores: sharing
+// this one there moved that kernel's register counts.)
+template <int MODE>
+__device__ __forceinline__ void ragged_tile(const uint8_t* src, uint8_t* dst, uint64_t L, uint32_t c0, uint32_t c1,
+                                            uint32_t ctr0, const ChachaRecord& R, uint32_t h[5], const PolyR32& PR,
+                                            uint32_t nct) {
+    for (uint32_t c = c0; c < c1; ++c) {
+        const uint64_t pos = 64ull * c;
+        const uint32_t nbytes = (uint32_t)min<uint64_t>(64, L - pos);
+        uint32_t w[16];
+        load_block(src + pos, nbytes, w, pos + nbytes >= 16);
+        uint32_t o[16];
+        chacha_block(R, ctr0 + c, o);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) o[i] ^= w[i];
+        store_block(dst + pos, nbytes, o);
+        if (MODE != MODE_XOR) {
+            uint32_t* ct = (MODE == MODE_SEAL) ? o : w;
+            if (MODE == MODE_SEAL && nbytes < 64) mask_tail(ct, nbytes);
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (4 * c + u < nct)
+                    poly32_block(h, PR, ct[4 * u], ct[4 * u + 1], ct[4 * u + 2], ct[4 * u + 3], 1u);
         }
     }
 }
@@ -218,24 +330,13 @@ __global__ __launch_bounds__(kSegThreads) void seg_kernel(SegParams p) {
         const uint64_t ioff = p.in_off[rec];
         const uint64_t L = p.in_off[rec + 1] - ioff;
         const uint64_t ooff = p.out_off[rec];
-        const uint32_t nb = (uint32_t)((L + 63) >> 6);
-        const uint32_t tb0 = tr * kTileBlocks;
-        const uint32_t tb1 = min(tb0 + kTileBlocks, nb);
-        const uint32_t c0 = min(tb0 + kSegBPL * j, tb1), c1 = min(c0 + kSegBPL, tb1);
+        const TileGeom G = tile_geom(L, tr, j);
+        const uint32_t tb0 = G.tb0, c0 = G.c0;
         const uint8_t* src = p.in + ioff;
         uint8_t* dst = p.out + ooff;
 
-        uint32_t kw[8], nw[3];
-        {
-            const uint32_t* kp = reinterpret_cast<const uint32_t*>(p.keys + (size_t)p.key_stride * rec);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) kw[i] = kp[i];
-            const uint32_t* np = reinterpret_cast<const uint32_t*>(p.nonces + 12ull * rec);
-#pragma unroll
-            for (int i = 0; i < 3; ++i) nw[i] = np[i];
-        }
         ChachaRecord R;
-        chacha_record_init(R, kw, nw);
+        seg_record_init(R, p, rec);
         const uint32_t ctr0 = seg_counter(p, rec);
 
         // Poly1305 state: lane 0 of the record's first tile absorbs the AAD prefix
@@ -248,25 +349,11 @@ __global__ __launch_bounds__(kSegThreads) void seg_kernel(SegParams p) {
             aad_len = E.aad_len;
             na = (aad_len + 15) >> 4;
             if (tr == 0 && j == 0 && na) {
-                const uint8_t* ap = p.aad + p.aad_off[rec];
-                for (uint32_t s = 0; s < na; ++s) {
-                    const uint32_t cnt = min(16u, aad_len - 16u * s);
-                    uint32_t w[4];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        uint32_t v = 0;
-#pragma unroll
-                        for (int b = 0; b < 4; ++b)
-                            if ((uint32_t)(4 * i + b) < cnt) v |= (uint32_t)ap[16 * s + 4 * i + b] << (8 * b);
-                        w[i] = v;
-                    }
-                    poly32_block(h, PR, w[0], w[1], w[2], w[3], 1u);
-                }
+                poly_absorb_aad(h, PR, p.aad + p.aad_off[rec], aad_len);
             }
         }
 
-        const bool whole = (uint64_t)(tb0 + kTileBlocks) * 64ull <= L;  // uniform over the workgroup
-        if (whole) {
+        if (G.whole) {
             // two stages of two blocks per lane; load / store instruction i serves the owners
             // 8i .. 8i+7 of the wave, eight lanes per owner = one whole 128-byte run each
             const uint32_t kk = lane & 7u;
@@ -336,41 +423,15 @@ __global__ __launch_bounds__(kSegThreads) void seg_kernel(SegParams p) {
                 }
             }
         } else {
-            // the record's ragged last tile: per lane, partial block masked
-            for (uint32_t c = c0; c < c1; ++c) {
-                const uint64_t pos = 64ull * c;
-                const uint32_t nbytes = (uint32_t)min<uint64_t>(64, L - pos);
-                uint32_t w[16];
-                load_block(src + pos, nbytes, w, pos + nbytes >= 16);
-                uint32_t o[16];
-                chacha_block(R, ctr0 + c, o);
-#pragma unroll
-                for (int i = 0; i < 16; ++i) o[i] ^= w[i];
-                store_block(dst + pos, nbytes, o);
-                if (kPoly) {
-                    uint32_t* ct = (MODE == MODE_SEAL) ? o : w;
-                    if (MODE == MODE_SEAL && nbytes < 64) mask_tail(ct, nbytes);
-#pragma unroll
-                    for (int u = 0; u < 4; ++u)
-                        if (4 * c + u < nct)
-                            poly32_block(h, PR, ct[4 * u], ct[4 * u + 1], ct[4 * u + 2], ct[4 * u + 3], 1u);
-                }
-            }
+            ragged_tile<MODE>(src, dst, L, G.c0, G.c1, ctr0, R, h, PR, nct);
         }
 
         if (kPoly) {
             // the lane holding the record's last block absorbs the length block
-            const bool last_tile = tb1 == nb;
-            const bool has_last = (c1 == nb && c1 > c0) || (nb == 0 && j == 0);
-            if (has_last) poly32_block(h, PR, aad_len, 0u, (uint32_t)L, (uint32_t)(L >> 32), 1u);
-            // positions (Poly1305 block index + 1) where this lane's and the tile's runs end
-            const uint32_t lane_end = na + min(4u * c1, nct) + (has_last ? 1u : 0u);
-            const uint32_t tile_end = na + min(4u * tb1, nct) + (last_tile ? 1u : 0u);
+            if (G.has_last()) poly32_block(h, PR, aad_len, 0u, (uint32_t)L, (uint32_t)(L >> 32), 1u);
             uint32_t l[5];
             h32_to_limbs(h, l);
-#ifndef ENET_SEG_PROBE_NO_SCALE  // timing probes (hand-built libraries only; wrong tags)
-            if (c1 > c0 || (tr == 0 && j == 0)) pscale(l, tile_end - lane_end, E.pw, min(E.nbits, 14u));
-#endif
+            if (G.c1 > G.c0 || (tr == 0 && j == 0)) pscale(l, G.tile_end(na, nct) - G.lane_end(na, nct), E.pw, min(E.nbits, 14u));
             wg_sum(l, red);
             // Publish the tile's partial; the record's last tile to arrive finishes the record.
             // Hand-off without an L2 write-back (MI355X_MICROARCH.md, inter-workgroup visibility,
@@ -387,9 +448,6 @@ __global__ __launch_bounds__(kSegThreads) void seg_kernel(SegParams p) {
                 last_flag = prev + 1 == E.ntiles ? 1u : 0u;
             }
             __syncthreads();
-#ifdef ENET_SEG_PROBE_NO_TAIL
-            last_flag = 0;
-#endif
             if (last_flag) {
                 const uint32_t nt = E.ntiles;
                 const uint32_t K = na + nct + 1;
@@ -418,22 +476,10 @@ __global__ __launch_bounds__(kSegThreads) void seg_kernel(SegParams p) {
                 }
                 if (j == kSegThreads - 1) load_part(nt - 1);  // already normalised at K
                 wg_sum(acc, red);
-                if (threadIdx.x == 0) {
-                    uint32_t tag[4];
-                    pfinish(acc, E.s, tag);
-                    if (MODE == MODE_SEAL) {
-                        uint32_t* tp = reinterpret_cast<uint32_t*>(p.tag_out + 16ull * rec);
-                        tp[0] = tag[0]; tp[1] = tag[1]; tp[2] = tag[2]; tp[3] = tag[3];
-                    } else {
-                        // a failed record's plaintext is zeroed by the record kernel launched
-                        // after this one (records_body: claimed records with ok == 0): zero
-                        // stores from here could be overtaken by other tiles' plaintext still
-                        // dirty in their XCD's L2
-                        const uint32_t* tp = reinterpret_cast<const uint32_t*>(p.tag_in + 16ull * rec);
-                        const uint32_t diff = (tag[0] ^ tp[0]) | (tag[1] ^ tp[1]) | (tag[2] ^ tp[2]) | (tag[3] ^ tp[3]);
-                        p.ok[rec] = diff == 0 ? 1 : 0;
-                    }
-                }
+                // a failed record's plaintext is zeroed by the record kernel launched after this
+                // one (records_body: claimed records with ok == 0): zero stores from here could
+                // be overtaken by other tiles' plaintext still dirty in their XCD's L2
+                if (threadIdx.x == 0) seg_tag_finish<MODE>(acc, E.s, p, rec);
             }
         }
         __syncthreads();  // the slab and red[] are reused by the next tile
@@ -449,15 +495,12 @@ __global__ __launch_bounds__(kSegThreads) void seg_kernel(SegParams p) {
 // launch whatever the launch does (profiles/r06b_long_kernel_stats.csv).
 
 // One tile of a record in XOR mode: lane j owns blocks [tb0 + 4j, +4) clipped to the record.
-__device__ __forceinline__ void xor_tile(const uint8_t* src, uint8_t* dst, uint64_t L, uint32_t tb0,
+__device__ __forceinline__ void xor_tile(const uint8_t* src, uint8_t* dst, uint64_t L, uint32_t tile,
                                          uint32_t ctr0, const ChachaRecord& R, uint8_t* slab) {
     const uint32_t lane = threadIdx.x & 63u, wbase = threadIdx.x & ~63u;
-    const uint32_t j = threadIdx.x;
-    const uint32_t nb = (uint32_t)((L + 63) >> 6);
-    const uint32_t tb1 = min(tb0 + kTileBlocks, nb);
-    const uint32_t c0 = min(tb0 + kSegBPL * j, tb1), c1 = min(c0 + kSegBPL, tb1);
-    const bool whole = (uint64_t)(tb0 + kTileBlocks) * 64ull <= L;  // uniform over the workgroup
-    if (whole) {
+    const TileGeom G = tile_geom(L, tile, threadIdx.x);
+    const uint32_t tb0 = G.tb0, c0 = G.c0;
+    if (G.whole) {
         const uint32_t kk = lane & 7u;
         const uint32_t msw = slab_sw(lane);
         uint8_t* wslab = slab + wbase * kRun;
@@ -481,9 +524,7 @@ __device__ __forceinline__ void xor_tile(const uint8_t* src, uint8_t* dst, uint6
         for (int st = 0; st < 2; ++st) {
             const uint32_t cb = ctr0 + c0 + 2u * st;  // u32 wrap (ChaCha20.cpp:110)
             uint32_t ka[16], kb[16];
-#ifndef ENET_SEG_PROBE_XOR_OLD
             chacha_block2(R, cb, cb + 1u, ka, kb);  // the keystream first, under the loads' latency
-#endif
             ENET_WAVE_LDS_SYNC();
 #pragma unroll
             for (int i = 0; i < 8; ++i)
@@ -503,9 +544,6 @@ __device__ __forceinline__ void xor_tile(const uint8_t* src, uint8_t* dst, uint6
                     pf[4 * i] = v.x; pf[4 * i + 1] = v.y; pf[4 * i + 2] = v.z; pf[4 * i + 3] = v.w;
                 }
             }
-#ifdef ENET_SEG_PROBE_XOR_OLD
-            chacha_block2(R, cb, cb + 1u, ka, kb);
-#endif
 #pragma unroll
             for (int i = 0; i < 16; ++i) { w2[i] ^= ka[i]; w2[16 + i] ^= kb[i]; }
             ENET_WAVE_LDS_SYNC();
@@ -521,17 +559,8 @@ __device__ __forceinline__ void xor_tile(const uint8_t* src, uint8_t* dst, uint6
             }
         }
     } else {
-        for (uint32_t c = c0; c < c1; ++c) {
-            const uint64_t pos = 64ull * c;
-            const uint32_t nbytes = (uint32_t)min<uint64_t>(64, L - pos);
-            uint32_t w[16];
-            load_block(src + pos, nbytes, w, pos + nbytes >= 16);
-            uint32_t o[16];
-            chacha_block(R, ctr0 + c, o);
-#pragma unroll
-            for (int i = 0; i < 16; ++i) o[i] ^= w[i];
-            store_block(dst + pos, nbytes, o);
-        }
+        uint32_t h[5] = {0, 0, 0, 0, 0};  // no Poly1305 in XOR mode
+        ragged_tile<MODE_XOR>(src, dst, L, G.c0, G.c1, ctr0, R, h, PolyR32{}, 0);
     }
 }
 
@@ -542,29 +571,20 @@ __global__ __launch_bounds__(kSegThreads) void seg_uniform_xor_kernel(SegParams 
     const uint64_t Lr = p.in_off[rec + 1] - ioff;
     const bool as_hinted = p.in_off[rec + 1] >= ioff && Lr == L;
     if (!as_hinted && tr != 0) return;  // the record's tile-0 workgroup runs it whole
-    uint32_t kw[8], nw[3];
-    {
-        const uint32_t* kp = reinterpret_cast<const uint32_t*>(p.keys + (size_t)p.key_stride * rec);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) kw[i] = kp[i];
-        const uint32_t* np = reinterpret_cast<const uint32_t*>(p.nonces + 12ull * rec);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) nw[i] = np[i];
-    }
     ChachaRecord R;
-    chacha_record_init(R, kw, nw);
+    seg_record_init(R, p, rec);
     const uint32_t ctr0 = seg_counter(p, rec);
     const uint8_t* src = p.in + ioff;
     uint8_t* dst = p.out + p.out_off[rec];
     if (as_hinted) {
-        xor_tile(src, dst, L, tr * kTileBlocks, ctr0, R, slab);
+        xor_tile(src, dst, L, tr, ctr0, R, slab);
         return;
     }
     // the hint was wrong for this record: all of it here (empty or disordered offsets: nothing)
     if (p.in_off[rec + 1] < ioff) return;
     const uint64_t ntile = (Lr + kTileBytes - 1) / kTileBytes;
     for (uint64_t t = 0; t < ntile; ++t) {
-        xor_tile(src, dst, Lr, (uint32_t)(t * kTileBlocks), ctr0, R, slab);
+        xor_tile(src, dst, Lr, (uint32_t)t, ctr0, R, slab);
         __syncthreads();  // the slab is reused by the next tile
     }
 }
@@ -605,11 +625,7 @@ constexpr uint32_t kUPow = 44;                      // LDS table entries r^(2^k)
 // Arrival counters per record: a top counter and kUGroups group counters, each on its own 128-byte
 // line.  Tile t arrives at group t mod kUGroups; a group's last arriver arrives at the top counter.
 // (One counter per record took all of a 32 MiB record's 512 arrivals at one address.)
-#ifdef ENET_SEG_PROBE_GROUPS
-constexpr uint32_t kUGroups = ENET_SEG_PROBE_GROUPS;  // timing probe
-#else
 constexpr uint32_t kUGroups = 16;
-#endif
 constexpr uint32_t kUArrStride = 32 * (1 + kUGroups);
 
 typedef uint32_t enet_v4u __attribute__((ext_vector_type(4)));
@@ -632,18 +648,7 @@ __device__ __forceinline__ void lds_barrier() {
 
 // Sum of the first `nwaves` waves' accumulators into thread 0's l (the others contribute zero).
 __device__ __forceinline__ void wg_sum5(uint32_t l[5], uint32_t* red /* [waves][5] shared */, uint32_t nwaves) {
-#pragma unroll
-    for (int off = 1; off <= 8; off <<= 1) {
-#pragma unroll
-        for (int i = 0; i < 5; ++i) l[i] += __shfl_xor(l[i], off);
-    }
-    pcarry(l);
-#pragma unroll
-    for (int off = 16; off <= 32; off <<= 1) {
-#pragma unroll
-        for (int i = 0; i < 5; ++i) l[i] += __shfl_xor(l[i], off);
-    }
-    pcarry(l);
+    wave_sum(l);
     const uint32_t w = threadIdx.x >> 6;
     if ((threadIdx.x & 63u) == 0 && w < nwaves) {
 #pragma unroll
@@ -663,27 +668,13 @@ __device__ __forceinline__ void wg_sum5(uint32_t l[5], uint32_t* red /* [waves][
 
 // Per-tile sums of the data waves' accumulators: the power wave's lane h gets tile h's sum (waves
 // 4h..4h+3) -- the power wave stored no data, so its publishing waits for its own stores alone.
-// pw (whole tiles): the r^(2^k) table; wave t of a tile is first scaled by r^(1024 (3 - t)) (lane
-// j's run ends 16 (255 - j) blocks before the tile's end; the in-wave part of that scaling is the
-// caller's).
+// Every lane's accumulator is already normalised at its tile's end.
 template <int TPW>
-__device__ __forceinline__ void wg_sum_tiles(uint32_t l[5], uint32_t* red /* [4 TPW][5] shared */, const uint32_t* pw) {
+__device__ __forceinline__ void wg_sum_tiles(uint32_t l[5], uint32_t* red /* [4 TPW][5] shared */) {
     constexpr uint32_t kUTiles = TPW, kUData = kSegThreads * TPW;
-#pragma unroll
-    for (int off = 1; off <= 8; off <<= 1) {
-#pragma unroll
-        for (int i = 0; i < 5; ++i) l[i] += __shfl_xor(l[i], off);
-    }
-    pcarry(l);
-#pragma unroll
-    for (int off = 16; off <= 32; off <<= 1) {
-#pragma unroll
-        for (int i = 0; i < 5; ++i) l[i] += __shfl_xor(l[i], off);
-    }
-    pcarry(l);
-    const uint32_t w = threadIdx.x >> 6, wt = w & 3u;
+    wave_sum(l);
+    const uint32_t w = threadIdx.x >> 6;
     const bool data = threadIdx.x < kUData;
-    if (data && pw && wt < 3) pscale(l, (3u - wt) << 10, pw, 12u);  // wave-uniform
     if ((threadIdx.x & 63u) == 0 && data) {
 #pragma unroll
         for (int i = 0; i < 5; ++i) red[5 * w + i] = l[i];
@@ -739,17 +730,8 @@ __global__ __launch_bounds__(kSegThreads * TPW + 64) void seg_uniform_aead_kerne
     if (!as_hinted && tr != 0) return;  // the record's tile-0 workgroup runs it whole
     const uint8_t* src = p.in + ioff;
     uint8_t* dst = p.out + p.out_off[rec];
-    uint32_t kw[8], nw[3];
-    {
-        const uint32_t* kp = reinterpret_cast<const uint32_t*>(p.keys + (size_t)p.key_stride * rec);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) kw[i] = kp[i];
-        const uint32_t* np = reinterpret_cast<const uint32_t*>(p.nonces + 12ull * rec);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) nw[i] = np[i];
-    }
     ChachaRecord R;
-    chacha_record_init(R, kw, nw);
+    seg_record_init(R, p, rec);
     uint32_t aad_len = 0;
     uint64_t aoff = 0;
     if (p.aad) {
@@ -759,7 +741,6 @@ __global__ __launch_bounds__(kSegThreads * TPW + 64) void seg_uniform_aead_kerne
     const uint32_t na = (aad_len + 15) >> 4;
     const uint32_t nct = (uint32_t)((L + 15) >> 4);
     const uint32_t K = na + nct + 1;  // Poly1305 blocks
-    const uint32_t nb = (uint32_t)((L + 63) >> 6);
     const uint32_t nt = as_hinted ? T : (L ? (uint32_t)((L + kTileBytes - 1) / kTileBytes) : 1u);
     // combine geometry (main path): q right-aligned tiles per lane, q a power of two
     const uint32_t nw_t = nt - 1;
@@ -775,21 +756,16 @@ __global__ __launch_bounds__(kSegThreads * TPW + 64) void seg_uniform_aead_kerne
         // waves' keystream: without a raised priority each of its steps took ~1 us
         __builtin_amdgcn_s_setprio(3);
         uint32_t otk[16];
-#ifdef ENET_SEG_PROBE_NO_OTK
-        for (int i = 0; i < 16; ++i) otk[i] = R.k[i & 7];
-#else
         chacha_block(R, 0u, otk);
-#endif
         if (lane == 0) {
 #pragma unroll
             for (int i = 0; i < 8; ++i) ok_s[i] = otk[i];
         }
         __hip_atomic_store(&okr_s, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
-    // The power wave's table, built while the data waves run their tile (main path: right after
-    // the one-time key; barrier B publishes it).  Low (what a tile's own scaling reads): r^(2^k),
-    // k <= 12, and in lane i r^(16 i), the product of r^(2^(4+b)) over the bits b of i.  High (read
-    // only by the record's last arriver): r^(2^k), 13 <= k < top, and r^R.
+    // The power wave's tables, built while the data waves run their tile (barrier B publishes
+    // them).  Low (what a tile's own scaling reads): r^(2^k), k < 12, and t1_s.  High (read only by
+    // the record's last arriver): r^(2^k), 12 <= k < top, r^R and t2_s.
     uint32_t px[5];  // the power wave's running square
     auto put = [&](uint32_t k) {
         if (lane == 0) {
@@ -798,9 +774,6 @@ __global__ __launch_bounds__(kSegThreads * TPW + 64) void seg_uniform_aead_kerne
         }
     };
     auto power_low = [&]() {
-#ifdef ENET_SEG_PROBE_NO_TABLE
-        return;
-#endif
         pclamp(px, ok_s[0], ok_s[1], ok_s[2], ok_s[3]);
         // one chain at a time (few registers: this runs where the tile's key state is live).  The
         // power wave shares a SIMD with two data waves, so every step here is slow: only what a
@@ -829,9 +802,6 @@ __global__ __launch_bounds__(kSegThreads * TPW + 64) void seg_uniform_aead_kerne
         }
     };
     auto power_high = [&]() {
-#ifdef ENET_SEG_PROBE_NO_TABLE
-        return;
-#endif
         for (uint32_t k = 12; k < top; ++k) {
             put(k);
             psquare(px);
@@ -879,30 +849,12 @@ __global__ __launch_bounds__(kSegThreads * TPW + 64) void seg_uniform_aead_kerne
         }
         uint32_t prev_end = 0;
         for (uint32_t v = 0; v < nt; ++v) {
-            const uint32_t tb0 = v * kTileBlocks;
-            const uint32_t tb1 = min(tb0 + kTileBlocks, nb);
-            const uint32_t c0 = min(tb0 + kSegBPL * j, tb1), c1 = min(c0 + kSegBPL, tb1);
+            const TileGeom G = tile_geom(L, v, j);
+            const uint32_t c0 = G.c0, c1 = G.c1, tile_end = G.tile_end(na, nct);
             uint32_t h[5] = {0, 0, 0, 0, 0};
             uint32_t l[5] = {0, 0, 0, 0, 0};
-            const bool last_tile = tb1 == nb;
-            const uint32_t tile_end = na + min(4u * tb1, nct) + (last_tile ? 1u : 0u);
             if (!pwv && half == 0) {
-                if (v == 0 && j == 0) {
-                    const uint8_t* ap = p.aad + aoff;
-                    for (uint32_t s2 = 0; s2 < na; ++s2) {
-                        const uint32_t cnt = min(16u, aad_len - 16u * s2);
-                        uint32_t w[4];
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            uint32_t vv = 0;
-#pragma unroll
-                            for (int b2 = 0; b2 < 4; ++b2)
-                                if ((uint32_t)(4 * i + b2) < cnt) vv |= (uint32_t)ap[16 * s2 + 4 * i + b2] << (8 * b2);
-                            w[i] = vv;
-                        }
-                        poly32_block(h, PR, w[0], w[1], w[2], w[3], 1u);
-                    }
-                }
+                if (v == 0 && j == 0) poly_absorb_aad(h, PR, p.aad + aoff, aad_len);
                 for (uint32_t c = c0; c < c1; ++c) {
                     const uint64_t pos = 64ull * c;
                     const uint32_t nbytes = (uint32_t)min<uint64_t>(64, L - pos);
@@ -920,15 +872,12 @@ __global__ __launch_bounds__(kSegThreads * TPW + 64) void seg_uniform_aead_kerne
                         if (4 * c + u < nct)
                             poly32_block(h, PR, ct[4 * u], ct[4 * u + 1], ct[4 * u + 2], ct[4 * u + 3], 1u);
                 }
-                const bool has_last = (c1 == nb && c1 > c0) || (nb == 0 && j == 0);
-                if (has_last) poly32_block(h, PR, aad_len, 0u, (uint32_t)L, (uint32_t)(L >> 32), 1u);
+                if (G.has_last()) poly32_block(h, PR, aad_len, 0u, (uint32_t)L, (uint32_t)(L >> 32), 1u);
                 h32_to_limbs(h, l);
             }
             if (v == 0) __syncthreads();  // barrier B: the table in LDS
             if (!pwv && half == 0) {
-                const bool has_last = (c1 == nb && c1 > c0) || (nb == 0 && j == 0);
-                const uint32_t lane_end = na + min(4u * c1, nct) + (has_last ? 1u : 0u);
-                if (c1 > c0 || (v == 0 && j == 0)) pscale(l, tile_end - lane_end, pw_s, 13u);
+                if (c1 > c0 || (v == 0 && j == 0)) pscale(l, tile_end - G.lane_end(na, nct), pw_s, 13u);
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             wg_sum5(l, red, kSegThreads / 64);
@@ -943,12 +892,10 @@ __global__ __launch_bounds__(kSegThreads * TPW + 64) void seg_uniform_aead_kerne
     } else {
         const uint32_t tt = kUTiles * tr + half;  // tile index inside the record (the power wave: the first)
         const bool tile_ok = tt < T;              // the record's last workgroup may hold one tile only
-        const uint32_t tb0 = tt * kTileBlocks;
-        const uint32_t tb1 = min(tb0 + kTileBlocks, nb);
-        const uint32_t c0 = min(tb0 + kSegBPL * j, tb1), c1 = min(c0 + kSegBPL, tb1);
+        const TileGeom G = tile_geom(L, tt, j);
+        const uint32_t tb0 = G.tb0, c0 = G.c0, c1 = G.c1;
         // uniform over the tile's waves (an absent tile: the per-block path over no blocks)
-        const bool whole = tile_ok && (uint64_t)(tb0 + kTileBlocks) * 64ull <= L;
-        const bool first_iter = true;
+        const bool whole = tile_ok && G.whole;
         uint32_t h[5] = {0, 0, 0, 0, 0};
         auto barrier_a = [&]() {  // r / s in LDS: wait for the power wave's flag (no barrier)
             while (__hip_atomic_load(&okr_s, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0u)
@@ -957,22 +904,7 @@ __global__ __launch_bounds__(kSegThreads * TPW + 64) void seg_uniform_aead_kerne
             PR = polyr32_make(ok_s[0], ok_s[1], ok_s[2], ok_s[3]);
         };
         auto absorb_aad = [&]() {
-            if (tt == 0 && j == 0 && !pwv) {
-                const uint8_t* ap = p.aad + aoff;
-                for (uint32_t s = 0; s < na; ++s) {
-                    const uint32_t cnt = min(16u, aad_len - 16u * s);
-                    uint32_t w[4];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        uint32_t vv = 0;
-#pragma unroll
-                        for (int b = 0; b < 4; ++b)
-                            if ((uint32_t)(4 * i + b) < cnt) vv |= (uint32_t)ap[16 * s + 4 * i + b] << (8 * b);
-                        w[i] = vv;
-                    }
-                    poly32_block(h, PR, w[0], w[1], w[2], w[3], 1u);
-                }
-            }
+            if (tt == 0 && j == 0 && !pwv) poly_absorb_aad(h, PR, p.aad + aoff, aad_len);
         };
         if (whole) {
             const uint32_t kk = lane & 7u;
@@ -1023,30 +955,21 @@ __global__ __launch_bounds__(kSegThreads * TPW + 64) void seg_uniform_aead_kerne
                         asm volatile("" : "+v"(R.k[0])::"memory");
                     }
                 }
-                if (st == 0 && first_iter) {
+                if (st == 0) {
                     barrier_a();
-                    absorb_aad();
-                } else if (st == 0) {
-                    PR = polyr32_make(ok_s[0], ok_s[1], ok_s[2], ok_s[3]);
                     absorb_aad();
                 }
                 if (!pwv) {
-#ifndef ENET_SEG_PROBE_NO_POLY
                     if (MODE == MODE_OPEN) {
                         poly_block64(h, PR, w2);
                         poly_block64(h, PR, w2 + 16);
                     }
-#endif
 #pragma unroll
                     for (int i = 0; i < 16; ++i) { w2[i] ^= ka[i]; w2[16 + i] ^= kb[i]; }
-#ifndef ENET_SEG_PROBE_NO_POLY
                     if (MODE == MODE_SEAL) {
                         poly_block64(h, PR, w2);
                         poly_block64(h, PR, w2 + 16);
                     }
-#else
-                    h[0] ^= w2[0];
-#endif
                     ENET_WAVE_LDS_SYNC();
 #pragma unroll
                     for (int k = 0; k < 8; ++k)
@@ -1062,8 +985,7 @@ __global__ __launch_bounds__(kSegThreads * TPW + 64) void seg_uniform_aead_kerne
                 }
             }
         } else {
-            if (first_iter) barrier_a();
-            else PR = polyr32_make(ok_s[0], ok_s[1], ok_s[2], ok_s[3]);
+            barrier_a();
             absorb_aad();
             if (!pwv) {
                 for (uint32_t c = c0; c < c1; ++c) {
@@ -1100,30 +1022,19 @@ __global__ __launch_bounds__(kSegThreads * TPW + 64) void seg_uniform_aead_kerne
 
         // this tile's partial, normalised at the tile's end
         uint32_t l[5] = {0, 0, 0, 0, 0};
-        const bool last_tile = tb1 == nb;
-        const uint32_t tile_end = na + min(4u * tb1, nct) + (last_tile ? 1u : 0u);
-        const bool has_last = (c1 == nb && c1 > c0) || (nb == 0 && j == 0);
+        const uint32_t tile_end = G.tile_end(na, nct);
         if (!pwv) {
-            if (has_last) poly32_block(h, PR, aad_len, 0u, (uint32_t)L, (uint32_t)(L >> 32), 1u);
+            if (G.has_last()) poly32_block(h, PR, aad_len, 0u, (uint32_t)L, (uint32_t)(L >> 32), 1u);
             h32_to_limbs(h, l);
         }
-#ifdef ENET_SEG_PROBE_NO_PUBLISH
-        if (h[0] == 0x12345u) p.ok[rec] = 7;  // keep the Horner live
-        return;
-#endif
-        // the power wave skipped the tile's body: it builds the table here, where no tile data
-        // is live (inside the body its registers would count against every wave)
+        // the power wave built its tables before it came here
         if (threadIdx.x == 0) SEG_STAMP(2);
         if (threadIdx.x == kUData) SEG_STAMP(3);
-#ifndef ENET_SEG_PROBE_NO_SYNC
-        lds_barrier();  // barrier B: the table's low part in LDS
-#endif
+        lds_barrier();  // barrier B: the tables in LDS
         if (threadIdx.x == 0) SEG_STAMP(4);
 
-#ifndef ENET_SEG_PROBE_NO_SCALE
         if (!pwv) {
-            const uint32_t lane_end = na + min(4u * c1, nct) + (has_last ? 1u : 0u);
-            const uint32_t e = tile_end - lane_end;
+            const uint32_t e = tile_end - G.lane_end(na, nct);
             if (whole) {
                 // e = 16 (255 - j) (+1 in the record's last tile for lanes before the length
                 // block) = 16 (63 - lane) + 1024 (3 - wave of the tile): one table entry
@@ -1141,11 +1052,10 @@ __global__ __launch_bounds__(kSegThreads * TPW + 64) void seg_uniform_aead_kerne
                 pscale(l, e, pw_s, 13u);
             }
         }
-#endif
         // open: every wave drains its write-through plaintext before the arrival (the last arriver
         // may zero the record)
         if (MODE == MODE_OPEN) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        wg_sum_tiles<TPW>(l, red, nullptr);  // whole tiles: the wave factor is in the lane's entry
+        wg_sum_tiles<TPW>(l, red);
         // main path: each tile publishes (the power wave's lane h for tile h), takes a ticket; the
         // record's last tile to arrive finishes it
         uint32_t* ctr = arrivals + (size_t)kUArrStride * rec;  // [0] top, [32 (1 + g)] group g
@@ -1155,13 +1065,6 @@ __global__ __launch_bounds__(kSegThreads * TPW + 64) void seg_uniform_aead_kerne
 #pragma unroll
             for (int i = 0; i < 5; ++i) __hip_atomic_store(part + i, l[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef ENET_SEG_PROBE_ONECTR
-            uint32_t lf = 0;
-            if (lane == 0) {  // one add per workgroup at one counter per record
-                const uint32_t nw = min(kUTiles, T - kUTiles * tr);
-                lf = __hip_atomic_fetch_add(ctr, nw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + nw == T ? 1u : 0u;
-            }
-#else
             const uint32_t ng = min(T, kUGroups), g = tp % ng, members = (T - g + ng - 1) / ng;
             uint32_t* gc = ctr + 32 * (1 + g);
             const uint32_t prev = __hip_atomic_fetch_add(gc, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1171,15 +1074,10 @@ __global__ __launch_bounds__(kSegThreads * TPW + 64) void seg_uniform_aead_kerne
                 const uint32_t top_prev = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 lf = top_prev + 1 == ng ? 1u : 0u;
             }
-#endif
             if (lf) last_flag = 1u;
             if (lane == 0) SEG_STAMP(5);
         }
         lds_barrier();
-#ifdef ENET_SEG_PROBE_NO_TAIL
-        if (threadIdx.x == 0 && last_flag) __hip_atomic_store(ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return;
-#endif
         if (!last_flag) return;  // uniform over the workgroup
         if (threadIdx.x >= kSegThreads) return;  // the combine runs on the first tile's four waves
         const uint32_t* parts = p.partials + 8ull * ((size_t)rec * T);
@@ -1230,18 +1128,7 @@ __global__ __launch_bounds__(kSegThreads * TPW + 64) void seg_uniform_aead_kerne
                     for (int i = 0; i < 5; ++i) mm[i] = t2_s[5 * (64 * (3u - w) + 63u - lane) + i];
                     pmul_by(acc, mm);
                 }
-#pragma unroll
-                for (int off = 1; off <= 8; off <<= 1) {
-#pragma unroll
-                    for (int i = 0; i < 5; ++i) acc[i] += __shfl_xor(acc[i], off);
-                }
-                pcarry(acc);
-#pragma unroll
-                for (int off = 16; off <= 32; off <<= 1) {
-#pragma unroll
-                    for (int i = 0; i < 5; ++i) acc[i] += __shfl_xor(acc[i], off);
-                }
-                pcarry(acc);
+                wave_sum(acc);
                 if (lane == 0) {
 #pragma unroll
                     for (int i = 0; i < 5; ++i) red[5 * w + i] = acc[i];
@@ -1270,21 +1157,9 @@ __global__ __launch_bounds__(kSegThreads * TPW + 64) void seg_uniform_aead_kerne
     // write-through and drained before its arrival; the fallback's are this workgroup's own)
     if (threadIdx.x == 0) SEG_STAMP(6);
     if (threadIdx.x == 0) {
-        uint32_t tag[4];
-        pfinish(hf, ok_s + 4, tag);
-        if (MODE == MODE_SEAL) {
-            uint32_t* tp = reinterpret_cast<uint32_t*>(p.tag_out + 16ull * rec);
-            tp[0] = tag[0]; tp[1] = tag[1]; tp[2] = tag[2]; tp[3] = tag[3];
-        } else {
-            const uint32_t* tp = reinterpret_cast<const uint32_t*>(p.tag_in + 16ull * rec);
-            const uint32_t diff = (tag[0] ^ tp[0]) | (tag[1] ^ tp[1]) | (tag[2] ^ tp[2]) | (tag[3] ^ tp[3]);
-            p.ok[rec] = diff == 0 ? 1 : 0;
-            last_flag = diff == 0 ? 0u : 1u;  // reused: 1 = zero the record
-        }
+        const uint32_t diff = seg_tag_finish<MODE>(hf, ok_s + 4, p, rec);
+        if (MODE == MODE_OPEN) last_flag = diff == 0 ? 0u : 1u;  // reused: 1 = zero the record
     }
-#if defined(ENET_SEG_PROBE_NO_POLY) || defined(ENET_SEG_PROBE_NO_TABLE)
-    if (MODE == MODE_OPEN) return;  // timing probes: wrong tags, nothing to zero
-#endif
     if (MODE == MODE_OPEN) {
         __syncthreads();
         const uint32_t zt = as_hinted ? kSegThreads : kUThreads;  // the main path's combine: 4 waves

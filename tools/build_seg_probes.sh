@@ -1,8 +1,10 @@
 #!/bin/bash
-# Hand-built timing-probe libraries (wrong tags by design): segments.hip recompiled with one
-# or more ENET_SEG_PROBE_* switches (A+B), linked with the product's other objects into
-# ephemeralnet_amd/libenet_probe_<SWITCH>.so; tools/seg_probe.sh times them beside the shipping
-# library.  Run after `python -m ephemeralnet_amd.build`.
+# Hand-built probe library: segments.hip recompiled with -DENET_SEG_PROBE_<SWITCH>, linked with the
+# product's other objects into ephemeralnet_amd/libenet_probe_<SWITCH>.so.  TRACE is the one switch
+# segments.hip still reads (per-workgroup phase stamps; correct bytes): tools/seg_trace.py reads
+# the stamps, tools/seg_ab.sh times the library beside the shipping one.
+#   bash tools/build_seg_probes.sh TRACE
+# Run after `python -m ephemeralnet_amd.build`.
 set -euo pipefail
 cd "$(dirname "$0")/.."
 B=ephemeralnet_amd/build

@@ -1,6 +1,7 @@
 #!/bin/bash
-# A/B of hand-built seg probe libraries on tools/seg_bench.py (1 x 32 MiB, seal+open and XOR pairs):
-#   bash tools/seg_ab.sh OUT ship VARIANT...   (VARIANT = a libenet_probe_<VARIANT>.so)
+# The shipping library beside hand-built ones (tools/build_seg_probes.sh) on tools/seg_bench.py
+# (1 x 32 MiB, seal+open and XOR pairs); a TRACE library's phase stamps are dumped as well:
+#   bash tools/seg_ab.sh OUT ship TRACE   (a VARIANT other than ship = libenet_probe_<VARIANT>.so)
 set -o pipefail
 O=gpurun_out/$1; shift
 mkdir -p $O
