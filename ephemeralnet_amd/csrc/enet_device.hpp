@@ -15,6 +15,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+#include <utility>
+
 #include "chacha_lockstep_asm.hpp"
 
 namespace enet {
@@ -181,16 +184,17 @@ __device__ __forceinline__ void chacha_half_lockstep(uint32_t x[32]) {
 // compiler's inline-asm hazard check at every add / xor / rotate group boundary, and statements
 // naming only the words they touch make the register allocator shuffle words between VGPRs
 // (~15 v_mov per step) once the rounds are a loop; with all 32 words tied there is neither.
-// sh(base + k) runs after step k (k = 0..3), pinned there by compiler memory barriers.
+// sh(std::integral_constant<int, BASE + k>) runs after step k (k = 0..3), between compiler memory
+// barriers (a hook holds its register arithmetic in place itself: ENET_PIN in stream_common.hpp).
 struct NoStepHook {
     __device__ __forceinline__ void operator()(int) const {}
 };
 // BAR: s_barrier after every step (1), after steps 1 and 3 (2), after step 3 (4), never (0).
-template <bool DIAG, class SH = NoStepHook, int BAR = 1>
-__device__ __forceinline__ void chacha_half_lockstep2(uint32_t x[32], SH&& sh = SH{}, int base = 0) {
-    auto after = [&](int k) {
+template <bool DIAG, class SH = NoStepHook, int BAR = 1, int BASE = 0>
+__device__ __forceinline__ void chacha_half_lockstep2(uint32_t x[32], SH&& sh = SH{}) {
+    auto after = [&](auto k) {
         asm volatile("" ::: "memory");
-        sh(base + k);
+        sh(std::integral_constant<int, BASE + decltype(k)::value>{});
         asm volatile("" ::: "memory");
     };
     constexpr bool b0 = BAR == 1, b1 = BAR == 1 || BAR == 2, b2 = BAR == 1, b3 = BAR != 0;
@@ -201,22 +205,22 @@ __device__ __forceinline__ void chacha_half_lockstep2(uint32_t x[32], SH&& sh = 
     } while (0)
     if constexpr (DIAG) {
         ENET_LS_STEP(ENET_LS_D0, b0);
-        after(0);
+        after(std::integral_constant<int, 0>{});
         ENET_LS_STEP(ENET_LS_D1, b1);
-        after(1);
+        after(std::integral_constant<int, 1>{});
         ENET_LS_STEP(ENET_LS_D2, b2);
-        after(2);
+        after(std::integral_constant<int, 2>{});
         ENET_LS_STEP(ENET_LS_D3, b3);
-        after(3);
+        after(std::integral_constant<int, 3>{});
     } else {
         ENET_LS_STEP(ENET_LS_C0, b0);
-        after(0);
+        after(std::integral_constant<int, 0>{});
         ENET_LS_STEP(ENET_LS_C1, b1);
-        after(1);
+        after(std::integral_constant<int, 1>{});
         ENET_LS_STEP(ENET_LS_C2, b2);
-        after(2);
+        after(std::integral_constant<int, 2>{});
         ENET_LS_STEP(ENET_LS_C3, b3);
-        after(3);
+        after(std::integral_constant<int, 3>{});
     }
 #undef ENET_LS_STEP
 }

@@ -10,7 +10,12 @@
 //     pair schedule (enet_device.hpp: both waves of a SIMD meet at s_barrier after every 24
 //     ChaCha instructions, so their full-rate adds / xors pair up) and Poly1305, reading their
 //     stage from an LDS input slab and writing it to an LDS output slab.  No global memory
-//     instruction, no branch and no wait sits in their keystream.
+//     instruction, no branch and no wait sits in their keystream, and no Poly1305 either: a
+//     stage's Poly1305 runs behind its last keystream barrier in seal and open alike (open's is
+//     held there, stream_issue below: left to the compiler most of it went into the
+//     stage's first barrier intervals, and the C2 bench lost 1.2 %).
+//     The two compute waves of a SIMD run at equal issue priority: raising either half, or
+//     both, moved nothing.
 //   * 4 memory waves (one per SIMD) move the bytes: each serves two compute waves, issuing one
 //     instruction between two consecutive keystream barriers on a fixed schedule -- the 16 LDS
 //     DMAs (global_load_lds_dwordx4, whole 128-byte lines) of the next stage early in the stage,
@@ -60,11 +65,53 @@ __device__ constexpr StreamSched stream_sched(int v) {
          : v == 5 ? StreamSched{1, 1, 1, 1} : StreamSched{1, 3, 2, 3};
 }
 __device__ constexpr int stream_barf(int v) { return v == 4 ? 2 : v == 5 ? 4 : 1; }
+// Issue priority of the waves and the place of open's Poly1305.  One s_setprio per wave before its
+// stage loop, never flipped inside it.  Compute waves w, w + 4 and memory wave w + 8 share a SIMD,
+// 0-3 in its wave slot 0, 4-7 dispatched second, the memory waves third (tools/simd_map.py,
+// profiles/stream_simd_map.json).
+//   prio_old / prio_young: compute waves 0-3 / 4-7; prio_mem: the memory waves
+//   poly (open only): 0 where the compiler puts it -- open's ciphertext is in registers before the
+//   keystream, and 57 of a stage's 152 v_mad_u64_u32 land in the first barrier interval, 3-4 in
+//   each of sixteen later ones; 1 pinned behind the last keystream barrier, as seal's is by its
+//   data; 2 / 3 spread over the 76 intervals (PolySpreadHook) behind each step's rotates / behind
+//   each step's barrier
+// Numbers (ENET_STREAM_VAR in the tools build, C2 shape): 20 + k: priorities k & 3 = 0 young 1,
+// 1 old 1, 2 both 1, 3 both 2; memory waves 3 (k < 4) or 2; 30 / 31 / 32: poly 1 / 2 / 3.
+// The default kernel (every lane count; the memory schedule variants too) runs number
+// ENET_STREAM_ISSUE = 30: C2 bench 948.7 -> 960.4 GiB/s against 0; no priority setting moved it
+// (944-951), 31 gave 957.9, 32 929.8 (profiles/stream_issue_screen.jsonl).
+// -DENET_STREAM_ISSUE=n builds a candidate library for an A/B through bench.py
+// (tools/stream_issue_ab.sh); the placements are compared that way, since the tools build's
+// probe branches keep the compiler from moving open's Poly1305 and 0 compiles there as 1 does.
+#ifndef ENET_STREAM_ISSUE
+#define ENET_STREAM_ISSUE 30
+#endif
+struct StreamIssue {
+    int prio_old, prio_young, prio_mem, poly;
+};
+__device__ constexpr StreamIssue stream_issue(int v) {
+    int k = -1, poly = 0;
+    if (v >= 20 && v < 28) k = v - 20;
+    else if (v >= 30 && v <= 32) poly = v - 29;
+    if (k < 0) return StreamIssue{0, 0, 3, poly};
+    const int c = k & 3;
+    return StreamIssue{c == 0 ? 0 : c == 3 ? 2 : 1, c == 1 ? 0 : c == 3 ? 2 : 1, (k & 4) ? 2 : 3, poly};
+}
 // stores issued at or after the last DMA's position (a store shares a position only after the DMA)
 __device__ constexpr int stream_stores_after(StreamSched sc) {
     int n = 0;
     for (int s = 0; s < 16; ++s) n += (sc.sA + sc.sE * s >= sc.dA + 15 * sc.dE) ? 1 : 0;
     return n;
+}
+
+// probe (dbg 32768): wave w of the workgroup writes {entry shader clock, HW_ID, w} into 16 bytes
+// at 16 w of the workgroup's tag slots (12 waves = 192 of its (512 >> LOGP) * 16 >= 512 bytes)
+__device__ __forceinline__ void stream_where(const RecParams& p, int logp, uint32_t wave, uint32_t lane,
+                                             uint64_t t_entry) {
+    if (lane != 0 || !p.tag_out) return;
+    const uint32_t hw = __builtin_amdgcn_s_getreg(4 | (31 << 11));  // HW_REG_HW_ID, bits 0..31
+    uint32_t* d = reinterpret_cast<uint32_t*>(p.tag_out + 16ull * ((blockIdx.x * kStreamLanes) >> logp) + 16u * wave);
+    d[0] = (uint32_t)t_entry; d[1] = (uint32_t)(t_entry >> 32); d[2] = hw; d[3] = wave;
 }
 
 template <int LOGP, int MODE, int SCHED = 0>
@@ -74,6 +121,7 @@ __global__ __launch_bounds__(kStreamWG) void stream_kernel(RecParams p) {
     constexpr int kPos = kStreamSteps / BARF;      // barrier positions per stage
     constexpr uint32_t P = 1u << LOGP;
     constexpr bool kPoly = (MODE != MODE_XOR);
+    constexpr StreamIssue ISS = stream_issue(SCHED < 20 ? ENET_STREAM_ISSUE : SCHED);
     // input slab (DMA landing, read by the compute waves) and output slab (written by the compute
     // waves, stored by the memory waves); wave w's part is 8 KiB at 8 KiB w
     __shared__ __attribute__((aligned(16))) uint8_t s_in[kStreamLanes * kRun];
@@ -95,6 +143,10 @@ __global__ __launch_bounds__(kStreamWG) void stream_kernel(RecParams p) {
     constexpr int dbg = 0;
 #endif
     const bool stamp = (dbg & 16384) && threadIdx.x == 0 && p.tag_out;
+    // probe (dbg 32768, tools/simd_map.py): every wave notes the shader clock at entry and its
+    // HW_ID (wave slot, SIMD, CU) and writes both into the workgroup's tag slots at exit
+    uint64_t t_entry = 0;
+    if (__builtin_expect(dbg & 32768, 0)) t_entry = __builtin_amdgcn_s_memtime();
     uint64_t* stamps = reinterpret_cast<uint64_t*>(p.tag_out + 16ull * rec);
     if (__builtin_expect(stamp, 0)) {
         stamps[0] = __builtin_amdgcn_s_memrealtime();
@@ -131,7 +183,7 @@ __global__ __launch_bounds__(kStreamWG) void stream_kernel(RecParams p) {
         // the memory waves win issue arbitration: their one instruction per keystream barrier
         // interval then never waits behind the compute waves' VALU stream (C2: +1-2 %,
         // tools/prio_ab.sh 876/879/889 -> 893/896/899 GiB/s on one box)
-        if (!(dbg & 4096)) __builtin_amdgcn_s_setprio(3);
+        if (!(dbg & 4096)) __builtin_amdgcn_s_setprio(ISS.prio_mem);
         uint32_t offA[2], offAB[2];
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
@@ -242,6 +294,7 @@ __global__ __launch_bounds__(kStreamWG) void stream_kernel(RecParams p) {
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every store done (tamper zeroing)
         stream_barrier();  // F2
+        if (__builtin_expect(dbg & 32768, 0)) stream_where(p, LOGP, wave, lane, t_entry);
         return;
     }
 
@@ -308,6 +361,13 @@ __global__ __launch_bounds__(kStreamWG) void stream_kernel(RecParams p) {
 
     const uint32_t ff[16] = {kSigma0, kSigma1, kSigma2, kSigma3, R.k[0], R.k[1], R.k[2], R.k[3],
                              R.k[4], R.k[5], R.k[6], R.k[7], 0u, R.n[0], R.n[1], R.n[2]};
+    if constexpr (ISS.prio_old == ISS.prio_young) {
+        if constexpr (ISS.prio_old != 0) __builtin_amdgcn_s_setprio(ISS.prio_old);
+    } else if (wave >= 4u) {
+        if constexpr (ISS.prio_young != 0) __builtin_amdgcn_s_setprio(ISS.prio_young);
+    } else {
+        if constexpr (ISS.prio_old != 0) __builtin_amdgcn_s_setprio(ISS.prio_old);
+    }
     for (uint32_t st = 0; st < S; ++st) {
         // S0(st): the memory waves saw stage st land; this wave's output writes are done
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -349,6 +409,16 @@ __global__ __launch_bounds__(kStreamWG) void stream_kernel(RecParams p) {
         if (__builtin_expect(dbg & 2, 0)) {  // probe: no keystream, the barriers only
 #pragma unroll
             for (int k = 0; k < kPos; ++k) stream_barrier();
+        } else if constexpr (MODE == MODE_OPEN && ISS.poly >= 2) {
+            // the hook of poly 2 issues the step's barrier itself, behind its piece
+            using Hook = PolySpreadHook<ISS.poly == 2>;
+            constexpr int HB = ISS.poly == 2 ? 0 : 1;
+            Hook hook(h, PR, w);
+            chacha_half_lockstep2<true, Hook&, HB, 0>(x, hook);
+            [&]<int... DR>(std::integer_sequence<int, DR...>) {  // double rounds 1..9, steps 4..75
+                ((chacha_half_lockstep2<false, Hook&, HB, 8 * DR + 4>(x, hook),
+                  chacha_half_lockstep2<true, Hook&, HB, 8 * DR + 8>(x, hook)), ...);
+            }(std::make_integer_sequence<int, 9>{});
         } else {
             chacha_half_lockstep2<true, NoStepHook, BARF>(x);
 #pragma unroll
@@ -357,7 +427,12 @@ __global__ __launch_bounds__(kStreamWG) void stream_kernel(RecParams p) {
                 chacha_half_lockstep2<true, NoStepHook, BARF>(x);
             }
         }
-        if (MODE == MODE_OPEN && !(dbg & 4)) {
+        if constexpr (MODE == MODE_OPEN && ISS.poly == 1) {
+            // the ciphertext is held behind the last keystream barrier: Poly1305 runs after it
+#pragma unroll
+            for (int i = 0; i < 32; ++i) ENET_PIN(w[i]);
+        }
+        if (MODE == MODE_OPEN && ISS.poly < 2 && !(dbg & 4)) {
             poly_block64(h, PR, w);
             poly_block64(h, PR, w + 16);
         }
@@ -389,9 +464,9 @@ __global__ __launch_bounds__(kStreamWG) void stream_kernel(RecParams p) {
     stream_barrier();  // F1
     if (__builtin_expect(stamp, 0)) stamps[3 + S] = __builtin_amdgcn_s_memtime();
 
-    if (dbg & (256 | 2048 | 16384)) {  // 4 words at the workgroup's first tag slot: clk0, rt0, clk1, rt1
+    if (dbg & (256 | 2048 | 16384 | 32768)) {  // 4 words at the workgroup's first tag slot: clk0, rt0, clk1, rt1
         const uint64_t clk1 = __builtin_amdgcn_s_memtime(), rt1 = __builtin_amdgcn_s_memrealtime();
-        if (threadIdx.x == 0 && p.tag_out && !(dbg & (2048 | 16384))) {
+        if (threadIdx.x == 0 && p.tag_out && !(dbg & (2048 | 16384 | 32768))) {
             uint64_t* d = reinterpret_cast<uint64_t*>(p.tag_out + 16ull * rec);
             d[0] = clk0; d[1] = rt0; d[2] = clk1; d[3] = rt1;
         }
@@ -400,6 +475,7 @@ __global__ __launch_bounds__(kStreamWG) void stream_kernel(RecParams p) {
             stamps[4 + S] = __builtin_amdgcn_s_memtime();
             stamps[5 + S] = __builtin_amdgcn_s_memrealtime();
         }
+        if (dbg & 32768) stream_where(p, LOGP, wave, lane, t_entry);
         return;
     }
     uint32_t diff = 0;
@@ -447,6 +523,12 @@ __global__ __launch_bounds__(kStreamWG) void stream_kernel(RecParams p) {
     }
 }
 
+// seal and xor have no placement variants
+template <int MODE>
+constexpr int stream_issue_var(int v) {
+    return (MODE == MODE_OPEN || v < 30) ? v : 0;
+}
+
 template <int MODE>
 static hipError_t launch_stream_mode(const RecParams& p, uint32_t lanes, uint32_t blocks, hipStream_t s) {
     switch (lanes) {
@@ -461,6 +543,10 @@ static hipError_t launch_stream_mode(const RecParams& p, uint32_t lanes, uint32_
                 case 4: hipLaunchKernelGGL((stream_kernel<1, MODE, 4>), dim3(blocks), dim3(kStreamWG), 0, s, p); break;
                 case 5: hipLaunchKernelGGL((stream_kernel<1, MODE, 5>), dim3(blocks), dim3(kStreamWG), 0, s, p); break;
                 case 14: hipLaunchKernelGGL((stream_kernel<1, MODE, 14>), dim3(blocks), dim3(kStreamWG), 0, s, p); break;
+#define ENET_VAR(V) case V: hipLaunchKernelGGL((stream_kernel<1, MODE, stream_issue_var<MODE>(V)>), dim3(blocks), dim3(kStreamWG), 0, s, p); break;
+                ENET_VAR(20) ENET_VAR(21) ENET_VAR(22) ENET_VAR(23) ENET_VAR(24) ENET_VAR(25) ENET_VAR(26) ENET_VAR(27)
+                ENET_VAR(30) ENET_VAR(31) ENET_VAR(32)
+#undef ENET_VAR
                 default: hipLaunchKernelGGL((stream_kernel<1, MODE>), dim3(blocks), dim3(kStreamWG), 0, s, p); break;
             }
 #else
