@@ -15,6 +15,10 @@ Operations mirror the reference src/crypto API, batched (ShardianLabs/EphemeralN
                   src/security/StoreProof.cpp:109-146, src/core/Node.cpp:193-292
   session_keys   KeyManager::derive_key     src/network/KeyManager.cpp:74-92
   shamir_split/combine Shamir::split / combine src/crypto/Shamir.cpp:114-163
+  handshake_accept Node::perform_handshake's crypto into a SessionTable
+                  src/core/Node.cpp:1872-1926, src/network/KeyExchange.cpp:9-48
+  session_rotate KeyManager::rotate_if_needed over a SessionTable  src/network/KeyManager.cpp:56-92
+  key_exchange   KeyExchange::compute_public / derive_shared_secret src/network/KeyExchange.cpp:22-48
 """
 from __future__ import annotations
 
@@ -71,7 +75,23 @@ EXPORTS = [
     "enet_host_mode_probe", "enet_host_mode_auto", "enet_host_mode_for", "enet_pipeline_stats", "enet_device_numa_node",
     "enet_host_cpu_budget", "enet_host_pinned_bytes", "enet_host_plan", "enet_host_register",
     "enet_host_unregister", "enet_shamir_split_batch", "enet_shamir_combine_batch",
+    "enet_handshake_accept_batch", "enet_session_rotate_batch", "enet_key_exchange_batch",
 ]
+
+# verdicts of handshake_accept (enet_crypto.h)
+ENET_HS_BAD_PUBLIC, ENET_HS_OK, ENET_HS_BAD_POW, ENET_HS_BAD_SLOT = 0, 1, 2, 3
+
+
+class _SessionTable(C.Structure):
+    _fields_ = [
+        ("sessions", C.c_uint32),
+        ("secrets", C.c_void_p),
+        ("keys", C.c_void_p),
+        ("mid", C.c_void_p),
+        ("counters", C.c_void_p),
+        ("last_rotation", C.c_void_p),
+        ("live", C.c_void_p),
+    ]
 
 
 class HostStats(C.Structure):
@@ -205,6 +225,10 @@ def lib() -> C.CDLL:
         L.enet_host_unregister.argtypes = [vp]
         L.enet_shamir_split_batch.argtypes = [u32, vp, vp, u32, u32, vp, vp]
         L.enet_shamir_combine_batch.argtypes = [u32, u32, vp, vp, vp, vp, vp]
+        tp = C.POINTER(_SessionTable)
+        L.enet_handshake_accept_batch.argtypes = [tp, u32, vp, vp, vp, vp, vp, u32, u32, u32, C.c_int64, vp, vp]
+        L.enet_session_rotate_batch.argtypes = [tp, C.c_int64, C.c_int64, vp, vp]
+        L.enet_key_exchange_batch.argtypes = [u32, vp, vp, vp, vp, vp]
         for name in EXPORTS:
             getattr(L, name)
         _lib = L
@@ -461,6 +485,73 @@ def shamir_combine(indices, values, threshold: int, secrets_out, ok, stream=None
     n = int(ok.numel())
     _check(lib().enet_shamir_combine_batch(n, int(threshold), _ptr(indices), _ptr(values), _ptr(secrets_out),
                                            _ptr(ok), _stream(stream)), "enet_shamir_combine_batch")
+
+
+@dataclass
+class SessionTable:
+    """The device session table (enet_session_table): S slots of {shared secret, current session
+    key, the key's HMAC midstates, rotation counter, last rotation time, live flag}, all torch
+    device tensors.  `keys` and `mid` are what wire_seal_sessions / wire_open_sessions take
+    (b.keys = table.keys, sessions = S, mid = table.mid, session index = slot)."""
+    secrets: "object"        # uint8 [S,32]
+    keys: "object"           # uint8 [S,32]
+    mid: "object"            # int32 [S,16]
+    counters: "object"       # int64 [S] (the uint64 counter's bits)
+    last_rotation: "object"  # int64 [S], ns since the steady_clock epoch
+    live: "object"           # uint8 [S]
+
+    @property
+    def sessions(self) -> int:
+        return int(self.live.numel())
+
+    @classmethod
+    def empty(cls, sessions: int, device="cuda") -> "SessionTable":
+        """A zero-filled table of `sessions` slots (no slot live)."""
+        import torch
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=device)  # noqa: E731
+        return cls(z((sessions, 32), torch.uint8), z((sessions, 32), torch.uint8), z((sessions, 16), torch.int32),
+                   z((sessions,), torch.int64), z((sessions,), torch.int64), z((sessions,), torch.uint8))
+
+    def struct(self) -> _SessionTable:
+        t = _SessionTable()
+        t.sessions = self.sessions
+        t.secrets, t.keys, t.mid = _ptr(self.secrets), _ptr(self.keys), _ptr(self.mid)
+        t.counters, t.last_rotation, t.live = _ptr(self.counters), _ptr(self.last_rotation), _ptr(self.live)
+        return t
+
+
+def handshake_accept(table: SessionTable, peer_ids, remote_public, work_nonce, slot, local_id, local_private: int,
+                     local_public: int, difficulty: int, now_ticks: int, verdict, stream=None) -> None:
+    """The crypto of Node::perform_handshake (Node.cpp:1872-1926) for n peers: validate_public,
+    the handshake PoW at `difficulty` (0: skipped, work_nonce / peer_ids may be None), the shared
+    secret and the session key, written with its HMAC midstates into table slot slot[i] (None: i).
+    verdict uint8 [n] gets ENET_HS_*; a rejected record leaves its slot untouched.  peer_ids uint8
+    [n,32], remote_public int32 [n] (uint32 bits), work_nonce int64 [n], slot int32 [n], local_id
+    uint8 [32].  The slots of one batch must be distinct."""
+    n = int(verdict.numel())
+    t = table.struct()
+    _check(lib().enet_handshake_accept_batch(C.byref(t), n, _ptr(peer_ids), _ptr(remote_public), _ptr(work_nonce),
+                                             _ptr(slot), _ptr(local_id), local_private & 0xFFFFFFFF,
+                                             local_public & 0xFFFFFFFF, int(difficulty), int(now_ticks),
+                                             _ptr(verdict), _stream(stream)), "enet_handshake_accept_batch")
+
+
+def session_rotate(table: SessionTable, now_ticks: int, interval_ticks: int, rotated, stream=None) -> None:
+    """KeyManager::rotate_if_needed over the whole table: live slots whose last rotation is at
+    least interval_ticks before now_ticks get the next counter, a new key and midstates;
+    rotated uint8 [S] says which."""
+    t = table.struct()
+    _check(lib().enet_session_rotate_batch(C.byref(t), int(now_ticks), int(interval_ticks), _ptr(rotated),
+                                           _stream(stream)), "enet_session_rotate_batch")
+
+
+def key_exchange(private_keys, remote_public=None, public_out=None, secret_out=None, stream=None) -> None:
+    """KeyExchange::compute_public / derive_shared_secret for n keypairs: private_keys int32 [n]
+    (uint32 bits); public_out int32 [n] = 5^private mod 2^31-1; with remote_public int32 [n],
+    secret_out uint8 [n,32] = SHA-256(BE32(remote^private mod 2^31-1)).  Either output may be None."""
+    n = int(private_keys.numel())
+    _check(lib().enet_key_exchange_batch(n, _ptr(private_keys), _ptr(remote_public), _ptr(public_out),
+                                         _ptr(secret_out), _stream(stream)), "enet_key_exchange_batch")
 
 
 def chunk_counter(chunk_id: bytes) -> int:

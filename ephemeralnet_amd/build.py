@@ -24,7 +24,7 @@ OBJ = os.path.join(PKG, "build")
 LIB_TOOLS = os.path.join(PKG, "libenet_crypto_tools.so")
 OBJ_TOOLS = os.path.join(PKG, "build_tools")
 SOURCES = ["records.hip", "segments.hip", "stream.hip", "sha.hip", "pow.hip", "duplex.hip", "duplex_split.hip",
-           "shamir.hip", "shamir_host.cpp",
+           "shamir.hip", "shamir_host.cpp", "handshake.hip",
            "capi.cpp", "long_records.cpp", "chunk_hybrid.cpp", "crypto_api.cpp", "pipeline.cpp", "host_engine.cpp",
            "frame_queue.cpp", "host_batch.cpp", "host_topo.cpp"]
 HEADERS = ["enet_device.hpp", "enet_internal.hpp", "long_route.hpp", "record_route.hpp", "long_records.hpp", "records_body.hpp",

@@ -918,4 +918,80 @@ int enet_shamir_combine_batch(uint32_t n, uint32_t threshold, const uint8_t* ind
                       "shamir_combine launch");
 }
 
+static_assert((int)ENET_HS_BAD_PUBLIC == (int)enet::ENET_DEV_HS_BAD_PUBLIC && (int)ENET_HS_OK == (int)enet::ENET_DEV_HS_OK &&
+                  (int)ENET_HS_BAD_POW == (int)enet::ENET_DEV_HS_BAD_POW &&
+                  (int)ENET_HS_BAD_SLOT == (int)enet::ENET_DEV_HS_BAD_SLOT,
+              "the kernels' verdicts are the header's");
+
+// the session table's arrays: all present, rows 4-byte aligned, 64-bit columns 8-byte aligned
+static const char* session_table_fault(const enet_session_table* t) {
+    if (!t) return "NULL session table";
+    if (t->sessions == 0) return nullptr;
+    if (!t->secrets || !t->keys || !t->mid || !t->counters || !t->last_rotation || !t->live)
+        return "NULL session table array";
+    if (!aligned4(t->secrets) || !aligned4(t->keys) || !aligned4(t->mid))
+        return "session table secrets, keys and mid must be 4-byte aligned";
+    if ((reinterpret_cast<uintptr_t>(t->counters) & 7u) || (reinterpret_cast<uintptr_t>(t->last_rotation) & 7u))
+        return "session table counters and last_rotation must be 8-byte aligned";
+    return nullptr;
+}
+
+static enet::SessionTableParams session_table_params(const enet_session_table* t) {
+    return enet::SessionTableParams{t->sessions, t->secrets, t->keys, t->mid, t->counters, t->last_rotation, t->live};
+}
+
+int enet_handshake_accept_batch(const enet_session_table* t, uint32_t n, const uint8_t* peer_ids,
+                                const uint32_t* remote_public, const uint64_t* work_nonce, const uint32_t* slot,
+                                const uint8_t* local_id, uint32_t local_private, uint32_t local_public,
+                                uint32_t difficulty, int64_t now_ticks, uint8_t* verdict, void* stream) {
+    if (const char* f = session_table_fault(t)) return fail(ENET_EINVAL, (std::string("handshake_accept: ") + f).c_str());
+    if (difficulty > 255) return fail(ENET_EINVAL, "handshake_accept: difficulty must be 0 .. 255");
+    if (n == 0) return ENET_OK;
+    if (!remote_public || !verdict) return fail(ENET_EINVAL, "handshake_accept: NULL remote_public or verdict");
+    if (difficulty != 0 && (!work_nonce || !peer_ids || !local_id))
+        return fail(ENET_EINVAL, "handshake_accept: difficulty != 0 needs work_nonce, peer_ids and local_id");
+    if (!aligned4(peer_ids) || !aligned4(local_id) || !aligned4(remote_public) || !aligned4(slot) ||
+        (reinterpret_cast<uintptr_t>(work_nonce) & 7u))
+        return fail(ENET_EINVAL, "handshake_accept: peer_ids, local_id, remote_public, slot (4-byte) or work_nonce "
+                                 "(8-byte) misaligned");
+    enet::HandshakeParams p{};
+    p.table = session_table_params(t);
+    p.n = n;
+    p.peer_ids = peer_ids;
+    p.remote_public = remote_public;
+    p.work_nonce = work_nonce;
+    p.slot = slot;
+    p.local_id = local_id;
+    p.local_private = local_private;
+    p.local_public = local_public;
+    p.difficulty = difficulty;
+    p.now = now_ticks;
+    p.verdict = verdict;
+    return hip_status(enet::launch_handshake_accept(p, (hipStream_t)stream), "handshake_accept launch");
+}
+
+int enet_session_rotate_batch(const enet_session_table* t, int64_t now_ticks, int64_t interval_ticks,
+                              uint8_t* rotated, void* stream) {
+    if (const char* f = session_table_fault(t)) return fail(ENET_EINVAL, (std::string("session_rotate: ") + f).c_str());
+    if (interval_ticks < 0) return fail(ENET_EINVAL, "session_rotate: interval_ticks must be >= 0");
+    if (t->sessions == 0) return ENET_OK;
+    if (!rotated) return fail(ENET_EINVAL, "session_rotate: NULL rotated");
+    return hip_status(enet::launch_session_rotate(session_table_params(t), now_ticks, interval_ticks, rotated,
+                                                  (hipStream_t)stream),
+                      "session_rotate launch");
+}
+
+int enet_key_exchange_batch(uint32_t n, const uint32_t* private_keys, const uint32_t* remote_public,
+                            uint32_t* public_out, uint8_t* secret_out, void* stream) {
+    if (n == 0) return ENET_OK;
+    if (!private_keys) return fail(ENET_EINVAL, "key_exchange: NULL private_keys");
+    if (secret_out && !remote_public) return fail(ENET_EINVAL, "key_exchange: secret_out needs remote_public (NULL)");
+    if (!aligned4(private_keys) || !aligned4(remote_public) || !aligned4(public_out) || !aligned4(secret_out))
+        return fail(ENET_EINVAL, "key_exchange: private_keys, remote_public, public_out and secret_out must be "
+                                 "4-byte aligned");
+    return hip_status(enet::launch_key_exchange(n, private_keys, remote_public, public_out, secret_out,
+                                                (hipStream_t)stream),
+                      "key_exchange launch");
+}
+
 }  // extern "C"

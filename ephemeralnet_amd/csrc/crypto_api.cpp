@@ -1511,6 +1511,84 @@ std::vector<std::array<std::uint8_t, 32>> session_keys(std::span<const Key> secr
     return res;
 }
 
+KeyExchangeResult key_exchange(std::span<const std::uint32_t> privates, std::span<const std::uint32_t> remotes) {
+    const size_t n = privates.size();
+    if (!remotes.empty() && remotes.size() != n) throw std::invalid_argument("enet batch::key_exchange: size mismatch");
+    KeyExchangeResult res;
+    if (n == 0) return res;
+    return staged([&](Staging& st) {
+        const bool secrets = !remotes.empty();
+        auto* dp = (uint32_t*)st.get(S_IN, 4 * n);
+        auto* dr = secrets ? (uint32_t*)st.get(S_KEYS, 4 * n) : nullptr;
+        auto* dpub = (uint32_t*)st.get(S_OUT, 4 * n);
+        auto* dsec = secrets ? (uint8_t*)st.get(S_AUX, 32 * n) : nullptr;
+        st.h2d(dp, privates.data(), 4 * n);
+        if (secrets) st.h2d(dr, remotes.data(), 4 * n);
+        enet_check(enet_key_exchange_batch((uint32_t)n, dp, dr, dpub, dsec, st.s()), "key_exchange");
+        res.publics.resize(n);
+        st.d2h(res.publics.data(), dpub, 4 * n);
+        if (secrets) {
+            res.secrets.resize(n);
+            st.d2h(res.secrets.data(), dsec, 32 * n);
+        }
+        st.sync();
+        return res;
+    });
+}
+
+std::vector<HandshakeResult> handshake_accept(const PeerId& local_id, std::uint32_t local_private,
+                                              std::uint8_t difficulty, std::chrono::steady_clock::time_point now,
+                                              std::span<const HandshakeRequest> requests) {
+    const size_t n = requests.size();
+    std::vector<HandshakeResult> res(n);
+    if (n == 0) return res;
+    // 5^local_private mod 2^31-1 (KeyExchange::compute_public), one scalar on the host
+    std::uint64_t local_public = 1, base = 5;
+    for (std::uint32_t e = local_private; e != 0; e >>= 1) {
+        if (e & 1u) local_public = local_public * base % 2147483647ull;
+        base = base * base % 2147483647ull;
+    }
+    return staged([&](Staging& st) {
+        // inputs: peer ids [n][32] | nonces [n] u64 | publics [n] u32 | local id [32]
+        std::vector<uint8_t> in(44 * n + 32);
+        for (size_t i = 0; i < n; ++i) {
+            std::memcpy(in.data() + 32 * i, requests[i].peer_id.data(), 32);
+            std::memcpy(in.data() + 32 * n + 8 * i, &requests[i].work_nonce, 8);
+            std::memcpy(in.data() + 40 * n + 4 * i, &requests[i].remote_public, 4);
+        }
+        std::memcpy(in.data() + 44 * n, local_id.data(), 32);
+        auto* din = (uint8_t*)st.get(S_IN, in.size());
+        // the call's table, slot i for request i: secrets | keys | mid | counters | last_rotation | live
+        auto* dt = (uint8_t*)st.get(S_OUT, 145 * n);
+        auto* dv = (uint8_t*)st.get(S_OK, n);
+        st.h2d(din, in.data(), in.size());
+        enet_session_table t{};
+        t.sessions = (uint32_t)n;
+        t.secrets = dt;
+        t.keys = dt + 32 * n;
+        t.mid = (uint32_t*)(dt + 64 * n);
+        t.counters = (uint64_t*)(dt + 128 * n);
+        t.last_rotation = (int64_t*)(dt + 136 * n);
+        t.live = dt + 144 * n;
+        const auto ticks = std::chrono::duration_cast<std::chrono::nanoseconds>(now.time_since_epoch()).count();
+        enet_check(enet_handshake_accept_batch(&t, (uint32_t)n, din, (const uint32_t*)(din + 40 * n),
+                                               (const uint64_t*)(din + 32 * n), nullptr, din + 44 * n, local_private,
+                                               (uint32_t)local_public, difficulty, ticks, dv, st.s()),
+                   "handshake_accept");
+        std::vector<uint8_t> verdict(n), rows(64 * n);
+        st.d2h(verdict.data(), dv, n);
+        st.d2h(rows.data(), dt, 64 * n);
+        st.sync();
+        for (size_t i = 0; i < n; ++i) {
+            res[i].verdict = (HandshakeVerdict)verdict[i];
+            if (verdict[i] != ENET_HS_OK) continue;  // rejected slots were never written
+            std::memcpy(res[i].shared_secret.bytes.data(), rows.data() + 32 * i, 32);
+            std::memcpy(res[i].session_key.data(), rows.data() + 32 * n + 32 * i, 32);
+        }
+        return res;
+    });
+}
+
 }  // namespace batch
 }  // namespace ephemeralnet::crypto
 

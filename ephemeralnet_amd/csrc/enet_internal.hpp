@@ -158,6 +158,41 @@ hipError_t launch_hmac_midstates(uint32_t n, const uint8_t* keys, uint32_t* mid,
 hipError_t launch_session_keys(uint32_t n, const uint8_t* secrets, const uint64_t* counters,
                                const int64_t* ticks, uint8_t* out, hipStream_t s);
 
+// ---- device session table (handshake.hip): the enet_session_table of the C ABI, by value
+struct SessionTableParams {
+    uint32_t sessions;
+    uint8_t* secrets;        // [S][32]
+    uint8_t* keys;           // [S][32]
+    uint32_t* mid;           // [S][16], the launch_hmac_midstates layout
+    uint64_t* counters;      // [S]
+    int64_t* last_rotation;  // [S]
+    uint8_t* live;           // [S]
+};
+// verdicts (ENET_HS_* of enet_crypto.h)
+enum : uint8_t { ENET_DEV_HS_BAD_PUBLIC = 0, ENET_DEV_HS_OK = 1, ENET_DEV_HS_BAD_POW = 2, ENET_DEV_HS_BAD_SLOT = 3 };
+struct HandshakeParams {
+    SessionTableParams table;
+    uint32_t n;
+    const uint8_t* peer_ids;        // [n][32], read only when difficulty != 0
+    const uint32_t* remote_public;  // [n]
+    const uint64_t* work_nonce;     // [n], nullable when difficulty == 0
+    const uint32_t* slot;           // [n], nullable -> i
+    const uint8_t* local_id;        // [32]
+    uint32_t local_private, local_public, difficulty;
+    int64_t now;
+    uint8_t* verdict;               // [n]
+};
+// Node::perform_handshake's crypto for n peers into the table; rows and local_id 4-byte aligned,
+// slots of one batch distinct (checked / documented by the C ABI)
+hipError_t launch_handshake_accept(const HandshakeParams& p, hipStream_t s);
+// KeyManager::rotate_if_needed over the whole table; rotated [S]
+hipError_t launch_session_rotate(const SessionTableParams& t, int64_t now, int64_t interval, uint8_t* rotated,
+                                 hipStream_t s);
+// KeyExchange::compute_public / derive_shared_secret for n keypairs; remotes, public_out and
+// secret_out nullable
+hipError_t launch_key_exchange(uint32_t n, const uint32_t* privates, const uint32_t* remotes, uint32_t* public_out,
+                               uint8_t* secret_out, hipStream_t s);
+
 // Shamir split / combine of 32-byte secrets over GF(2^8)/0x11D (shamir.hip); 1 <= threshold <=
 // share_count <= 255, the 32-byte-row buffers 4-byte aligned (checked by the C ABI)
 hipError_t launch_shamir_split(uint32_t n, const uint8_t* secrets, const uint8_t* coeffs, uint32_t threshold,

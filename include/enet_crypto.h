@@ -245,6 +245,64 @@ ENET_API int enet_shamir_combine_batch(uint32_t n, uint32_t threshold, const uin
                                        const uint8_t* values, uint8_t* secrets_out, uint8_t* ok,
                                        void* stream);
 
+/* ---- device session table: batched handshake admission and key rotation
+ *      (additive to ABI 1.4: enet_abi_version() is unchanged, no existing call changes)
+ * The crypto of Node::perform_handshake (src/core/Node.cpp:1872-1926) for many peers at once, and
+ * KeyManager's rotation, with the session keys born and rotated in device memory: `keys` and `mid`
+ * of the table are exactly the keys table and the enet_hmac_midstates of
+ * enet_wire_seal_batch_sessions / enet_wire_open_batch_sessions (session index = slot), so a
+ * later call on the same stream uses an admitted or rotated key with no upload and no midstate
+ * pass.  All table arrays are device memory owned by the caller; secrets, keys and mid must be
+ * 4-byte aligned, counters and last_rotation 8-byte aligned.  last_rotation is in ns since the
+ * steady_clock epoch (the ticks of enet_session_key_batch). */
+typedef struct enet_session_table {
+    uint32_t sessions;       /* S */
+    uint8_t* secrets;        /* [S][32] shared secrets (KeyExchange::derive_shared_secret) */
+    uint8_t* keys;           /* [S][32] current session keys */
+    uint32_t* mid;           /* [S][16] == enet_hmac_midstates(keys) */
+    uint64_t* counters;      /* [S] rotation counters */
+    int64_t* last_rotation;  /* [S] */
+    uint8_t* live;           /* [S] 1 = the slot holds a session */
+} enet_session_table;
+enum { ENET_HS_BAD_PUBLIC = 0, ENET_HS_OK = 1, ENET_HS_BAD_POW = 2, ENET_HS_BAD_SLOT = 3 };
+/* Record i, in the reference's order:
+ *   1. KeyExchange::validate_public(remote_public[i]) (1 < c < 2^31-1), else ENET_HS_BAD_PUBLIC;
+ *   2. when difficulty != 0, handshake_pow_valid (Node.cpp:232-256): leading zero bits of
+ *      SHA-256(BE64(32) || peer_ids[i] || BE64(32) || local_id || BE64(remote_public[i]) ||
+ *      BE64(work_nonce[i])) >= difficulty, else ENET_HS_BAD_POW.  difficulty == 0 skips the check
+ *      (work_nonce and peer_ids may then be NULL); it is also the initiator's side, which admits
+ *      the responder without a proof;
+ *   3. slot[i] (NULL: i) < sessions, else ENET_HS_BAD_SLOT;
+ *   4. secret = derive_shared_secret(local_private, remote_public[i]) (KeyExchange.cpp:34-48),
+ *      key = HMAC-SHA256(secret, BE32(min(local_public, remote)) || BE32(max(..)))
+ *      (make_handshake_material, Node.cpp:61-75; register_session_with_material,
+ *      KeyManager.cpp:32-46), and the slot becomes {secret, key, midstates of key, counter 0,
+ *      last_rotation now_ticks, live 1}; verdict[i] = ENET_HS_OK.
+ * A rejected record writes its verdict only: its slot stays byte for byte as it was.
+ * Caller contract: the slots of one batch are distinct (two records of one batch never name the
+ * same slot); a slot that is already live is replaced, as contexts_[peer] = context does.
+ * peer_ids [n][32] and local_id [32] must be 4-byte aligned.  ENET_EINVAL (nothing launched) for
+ * a NULL required buffer, a misaligned one, difficulty > 255, or difficulty != 0 without
+ * work_nonce / peer_ids.  n == 0 is a no-op. */
+ENET_API int enet_handshake_accept_batch(const enet_session_table* t, uint32_t n, const uint8_t* peer_ids,
+                                         const uint32_t* remote_public, const uint64_t* work_nonce,
+                                         const uint32_t* slot, const uint8_t* local_id, uint32_t local_private,
+                                         uint32_t local_public, uint32_t difficulty, int64_t now_ticks,
+                                         uint8_t* verdict, void* stream);
+/* KeyManager::rotate_if_needed + derive_key (KeyManager.cpp:56-92) over the whole table: slot s
+ * with live[s] != 0 and now_ticks - last_rotation[s] >= interval_ticks gets counters[s] += 1
+ * (uint64 wrap), last_rotation[s] = now_ticks, keys[s] = HMAC-SHA256(secrets[s], BE64(counter) ||
+ * BE64(now_ticks)), fresh mid[s], and rotated[s] = 1; every other slot gets rotated[s] = 0 and is
+ * not written.  rotated [S].  ENET_EINVAL for interval_ticks < 0; sessions == 0 is a no-op. */
+ENET_API int enet_session_rotate_batch(const enet_session_table* t, int64_t now_ticks, int64_t interval_ticks,
+                                       uint8_t* rotated, void* stream);
+/* KeyExchange::compute_public / derive_shared_secret (KeyExchange.cpp:22-48) for n keypairs:
+ * public_out[i] = 5^private_keys[i] mod 2^31-1; when remote_public is given,
+ * secret_out[i] ([n][32], 4-byte aligned) = SHA-256(BE32((remote_public[i] mod P)^private_keys[i]
+ * mod P)).  public_out or secret_out may be NULL (secret_out needs remote_public). */
+ENET_API int enet_key_exchange_batch(uint32_t n, const uint32_t* private_keys, const uint32_t* remote_public,
+                                     uint32_t* public_out, uint8_t* secret_out, void* stream);
+
 /* ---- host-resident pipeline
  * The reference's crypto path starts and ends in host memory (socket / relay buffers,
  * SessionManager.cpp:362-387 and 815-822; chunk files, Node.cpp:1414-1417 and 1641-1655).  These

@@ -377,4 +377,44 @@ ENET_CXX_API std::vector<std::array<std::uint8_t, 32>> session_keys(std::span<co
                                                                     std::span<const std::uint64_t> counters,
                                                                     std::span<const std::int64_t> ticks);
 
+// KeyExchange::compute_public / derive_shared_secret (src/network/KeyExchange.cpp:22-48) for many
+// keypairs in one device pass (enet_key_exchange_batch): publics[i] = 5^privates[i] mod 2^31-1 and,
+// when `remotes` is not empty (then one per private), secrets[i] = derive_shared_secret(privates[i],
+// remotes[i]).  std::invalid_argument for a size mismatch.
+struct KeyExchangeResult {
+    std::vector<std::uint32_t> publics;
+    std::vector<Key> secrets;  // empty when no remotes were given
+};
+ENET_CXX_API KeyExchangeResult key_exchange(std::span<const std::uint32_t> privates,
+                                            std::span<const std::uint32_t> remotes);
+
+// The crypto of Node::perform_handshake (src/core/Node.cpp:1872-1926) for many peers in one device
+// pass (enet_handshake_accept_batch on a table of requests.size() slots that lives for the call):
+// per request, in the reference's order, KeyExchange::validate_public, handshake_pow_valid at
+// `difficulty` (0 = no check: the initiator's side) with `local_id` as the responder, then
+// derive_shared_secret(local_private, remote_public) and the session key
+// HMAC(secret, make_handshake_material(local public, remote_public)).  An accepted result
+// (verdict == HandshakeVerdict::Ok) feeds KeyManager unchanged:
+//   register_session_with_material(peer_id, r.shared_secret, make_handshake_material(..), now)
+// leaves current_key(peer_id) == r.session_key, which is also what
+// SessionManager::register_peer_key takes.  A rejected result carries zero bytes.  Host-vector
+// callers keep their own peer -> session maps, cooldowns and reputation: nothing is deduplicated
+// here, and two requests of one peer are simply two results.  Device-resident callers use the C
+// ABI's session table, where the keys never leave the device.
+enum class HandshakeVerdict : std::uint8_t { BadPublic = 0, Ok = 1, BadPow = 2, BadSlot = 3 };
+struct HandshakeRequest {
+    PeerId peer_id{};
+    std::uint32_t remote_public{0};
+    std::uint64_t work_nonce{0};
+};
+struct HandshakeResult {
+    HandshakeVerdict verdict{HandshakeVerdict::BadPublic};
+    Key shared_secret{};
+    std::array<std::uint8_t, 32> session_key{};
+};
+ENET_CXX_API std::vector<HandshakeResult> handshake_accept(const PeerId& local_id, std::uint32_t local_private,
+                                                           std::uint8_t difficulty,
+                                                           std::chrono::steady_clock::time_point now,
+                                                           std::span<const HandshakeRequest> requests);
+
 }  // namespace ephemeralnet::crypto::batch
