@@ -28,7 +28,7 @@ SOURCES = ["records.hip", "segments.hip", "stream.hip", "sha.hip", "pow.hip", "d
            "capi.cpp", "long_records.cpp", "chunk_hybrid.cpp", "crypto_api.cpp", "pipeline.cpp", "host_engine.cpp",
            "frame_queue.cpp", "host_batch.cpp", "host_topo.cpp"]
 HEADERS = ["enet_device.hpp", "enet_internal.hpp", "long_route.hpp", "record_route.hpp", "long_records.hpp", "records_body.hpp",
-           "stream_common.hpp", "host_engine.hpp", "scalar.hpp", "host_batch.hpp", "host_topo.hpp", "gf256.hpp"]
+           "stream_common.hpp", "duplex_common.hpp", "host_engine.hpp", "scalar.hpp", "host_batch.hpp", "host_topo.hpp", "gf256.hpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC",
           "-fvisibility=hidden", "-Wall", "-Wno-unused-function",
@@ -37,7 +37,7 @@ LDFLAGS = ["--offload-arch=gfx950", "-fPIC", "-shared"]
 
 
 DEVICE_HEADERS = ["enet_device.hpp", "enet_internal.hpp", "long_route.hpp", "record_route.hpp", "records_body.hpp", "stream_common.hpp",
-                  "chacha_lockstep_asm.hpp", "gf256.hpp"]
+                  "duplex_common.hpp", "chacha_lockstep_asm.hpp", "gf256.hpp"]
 
 
 def _headers(src: str = "") -> list[str]:

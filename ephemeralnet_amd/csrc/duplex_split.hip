@@ -30,31 +30,15 @@
 // seal/open + HMAC-SHA256_K(m), HmacSha256.cpp:11-39).  Frames keep duplex.hip (their MAC sits
 // inside the ciphertext).  A record whose output length differs from its input is not
 // processed: output zeroed, ok = 0.
-#include "enet_device.hpp"
-#include "enet_internal.hpp"
+#include "duplex_common.hpp"
 
 namespace enet {
 
 namespace {
 
-constexpr uint32_t kSRun = 128;  // bytes per stage and record
+constexpr uint32_t kSRun = kDxRun;
 constexpr uint32_t kSRec = 64;   // records per workgroup (one lane each in 4 waves)
 constexpr uint32_t kSWaves = 4;  // C0, C1, S, R
-
-#define ENET_SP_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-
-__device__ __forceinline__ void sp_keep_le(uint32_t* w, int n, uint32_t r) {
-    for (int j = 0; j < n; ++j) {
-        const uint32_t b = 4u * j;
-        const uint32_t m = b + 4u <= r ? 0xffffffffu : (b >= r ? 0u : (1u << (8u * (r - b))) - 1u);
-        w[j] &= m;
-    }
-}
-
-__device__ __forceinline__ void sp_zero_bytes(uint8_t* p, uint64_t n) {
-    const uint32_t z[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    for (uint64_t o = 0; o < n; o += 64) store_block(p + o, (uint32_t)min<uint64_t>(64, n - o), z);
-}
 
 // W[16..63] from W[0..15] (Sha256.cpp:134-150)
 __device__ __forceinline__ void sha256_expand(uint32_t w[64]) {
@@ -95,28 +79,14 @@ __global__ __launch_bounds__(kSWaves * kSRec) void duplex_split_kernel(DuplexPar
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t pos = blockIdx.x * kSRec + lane;
-    const bool live = pos < p.n;
-    const uint32_t rec = live ? (p.order ? p.order[pos] : pos) : 0u;
-
     // ---- geometry (every role computes it)
-    uint64_t ib = 0, Li = 0, ob = 0, Lo = 0;
-    bool ordered = true;
-    if (live) {
-        ib = p.in_off[rec];
-        const uint64_t ie = p.in_off[rec + 1];
-        ob = p.out_off[rec];
-        const uint64_t oe = p.out_off[rec + 1];
-        ordered = ie >= ib && oe >= ob;
-        Li = ordered ? ie - ib : 0u;
-        Lo = ordered ? oe - ob : 0u;
-    }
-    const bool valid = live && ordered && Lo == Li;
-    const uint64_t Lm = valid ? Li : 0u;
-    const uint32_t Ts = (uint32_t)(Lm / kSRun);
-    const uint32_t r = (uint32_t)(Lm - (uint64_t)kSRun * Ts);
-    const uint64_t tb = (uint64_t)kSRun * Ts;
-    const uint8_t* src = p.in + ib;
-    uint8_t* dst = p.out + ob;
+    DuplexGeom g = duplex_geom(p, pos);
+    duplex_geom_message(g, g.Li, g.Lo == g.Li);
+    const bool live = g.live, valid = g.valid;
+    const uint32_t rec = g.rec, Ts = g.Ts(), r = g.r();
+    const uint64_t Lm = g.Lm, tb = g.tb();
+    const uint8_t* src = p.in + g.ib;
+    uint8_t* dst = p.out + g.ob;
 
     if (threadIdx.x == 0) tmax_s = 0;
     __syncthreads();
@@ -192,7 +162,7 @@ __global__ __launch_bounds__(kSWaves * kSRec) void duplex_split_kernel(DuplexPar
 #pragma unroll
                     for (int i = 0; i < 16; ++i) w[i] ^= ka[i];
                     store_block(hdst + tb, rh, w);
-                    sp_keep_le(w, 16, rh);  // RFC 8439 zero pad / clean hash input
+                    keep_le<16>(w, rh);  // RFC 8439 zero pad / clean hash input
                 }
                 if (kHand) {
 #pragma unroll
@@ -203,28 +173,19 @@ __global__ __launch_bounds__(kSWaves * kSRec) void duplex_split_kernel(DuplexPar
             // a failed open is zeroed by R two intervals later: this wave's stores must be done
             // (only in intervals where one of its records ended)
             if (OPEN && __builtin_amdgcn_ballot_w64(t == Ts && valid)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            ENET_SP_BARRIER();
+            ENET_DX_BARRIER();
         }
     } else if (wave == 2) {
         // ================================================================ S: schedule + Poly1305
-        PolyR32 PR{};
-        uint32_t h[5] = {0, 0, 0, 0, 0}, pad[4] = {0, 0, 0, 0};
+        AeadLane A{};
         if (kAead) {
             uint32_t nw[3];
 #pragma unroll
             for (int i = 0; i < 3; ++i) nw[i] = live ? ld32(p.nonces + 12ull * rec + 4 * i) : 0u;
             ChachaRecord R;
             chacha_record_init(R, kw, nw);
-            uint32_t otk[16];
-            chacha_block(R, 0u, otk);  // one-time key = keystream block 0 (RFC 8439 2.6)
-            PR = polyr32_make(otk[0], otk[1], otk[2], otk[3]);
-            pad[0] = otk[4]; pad[1] = otk[5]; pad[2] = otk[6]; pad[3] = otk[7];
+            aead_lane_init(A, R);
         }
-        auto poly_words = [&](const uint32_t* w, uint32_t blocks) {
-#pragma unroll
-            for (uint32_t q = 0; q < 8; ++q)
-                if (q < blocks) poly32_block(h, PR, w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3], 1u);
-        };
         auto global_run = [&](uint32_t s, uint32_t* x) {
             const uint4* q = reinterpret_cast<const uint4*>(src + (uint64_t)kSRun * s);
 #pragma unroll
@@ -248,7 +209,7 @@ __global__ __launch_bounds__(kSWaves * kSRec) void duplex_split_kernel(DuplexPar
                     uint32_t ct[32];
                     if (OPEN) global_run(u, ct);  // the input is the ciphertext
                     else slab_run(u, ct);         // C's output
-                    poly_words(ct, 8);
+                    aead_absorb(A, ct, 8);
                 }
                 if (OPEN) slab_run(u, pt);  // C's output is the plaintext
                 else global_run(u, pt);     // the input is the plaintext (an L2 hit: C just read it)
@@ -284,44 +245,29 @@ __global__ __launch_bounds__(kSWaves * kSRec) void duplex_split_kernel(DuplexPar
                             if (r > 64u) load_block(src + tb + 64, r - 64u, ct + 16, tb + r >= 16u);
                         }
                     }
-                    poly_words(ct, (r + 15u) >> 4);
-                    poly32_block(h, PR, 0u, 0u, (uint32_t)Lm, (uint32_t)(Lm >> 32), 1u);  // LE64 |aad| = 0, LE64 |ct|
-                    uint32_t l[5], tag[4];
-                    h32_to_limbs(h, l);
-                    pfinish(l, pad, tag);
+                    aead_absorb(A, ct, (r + 15u) >> 4);
+                    uint32_t tag[4];
+                    aead_tag(A, Lm, tag);
                     if (OPEN) {  // verdict for R: this record's run-slab row of the other parity is free now
-                        const uint8_t* tp = p.tags_in + 16ull * rec;
-                        runs[(Ts + 1u) & 1u][0][lane].x = ((tag[0] ^ ld32(tp)) | (tag[1] ^ ld32(tp + 4)) |
-                                                            (tag[2] ^ ld32(tp + 8)) | (tag[3] ^ ld32(tp + 12))) == 0u;
+                        runs[(Ts + 1u) & 1u][0][lane].x = tag_diff(tag, p.tags_in + 16ull * rec) == 0u;
                     } else {
                         *reinterpret_cast<uint4*>(p.tags + 16ull * rec) = make_uint4(tag[0], tag[1], tag[2], tag[3]);
                     }
                 }
                 // message tail, 0x80, zeros, BE64 bit length of [ipad ||] m (Sha256.cpp:94-126)
                 const uint64_t bits = ((kAead ? 64ull : 0ull) + Lm) * 8ull;
-                const uint32_t nb = (r + 9u + 63u) >> 6;  // 1..3 blocks
 #pragma unroll
                 for (int k = 0; k < 3; ++k) {
                     uint32_t x[16];
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) {
-                        const uint32_t b = 64u * k + 4u * i;
-                        const uint32_t v = k < 2 ? bswap32(pt[16 * k + i]) : 0u;
-                        const uint32_t m = b + 4u <= r ? 0xffffffffu : (b >= r ? 0u : 0xffffffffu << (8u * (4u - (r - b))));
-                        x[i] = (v & m) | ((r >> 2) == (b >> 2) ? 0x80000000u >> (8u * (r & 3u)) : 0u);
-                    }
-                    if ((uint32_t)k == nb - 1u) {
-                        x[14] = (uint32_t)(bits >> 32);
-                        x[15] = (uint32_t)bits;
-                    }
-                    if ((uint32_t)k < nb) {
+                    sha256_tail_block(k, pt, r, bits, x);
+                    if ((uint32_t)k < sha256_tail_blocks(r)) {
 #pragma unroll
                         for (int c = 0; c < 4; ++c)
                             wsl[Ts & 1u][4 * k + c][lane] = make_uint4(x[4 * c], x[4 * c + 1], x[4 * c + 2], x[4 * c + 3]);
                     }
                 }
             }
-            ENET_SP_BARRIER();
+            ENET_DX_BARRIER();
         }
     } else {
         // ================================================================ R: rounds + finish
@@ -329,14 +275,8 @@ __global__ __launch_bounds__(kSWaves * kSRec) void duplex_split_kernel(DuplexPar
 #pragma unroll
         for (int i = 0; i < 8; ++i) kb[i] = bswap32(kw[i]);
         uint32_t st[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) st[i] = kShaIV[i];
-        if (kAead) {  // HMAC inner: the ipad block first (HmacSha256.cpp:24-29)
-            uint32_t x[16];
-#pragma unroll
-            for (int i = 0; i < 16; ++i) x[i] = (i < 8 ? kb[i] : 0u) ^ 0x36363636u;
-            sha256_compress(st, x);
-        }
+        if (kAead) hmac_key_state(st, kb, kHmacIpad);  // HMAC inner: the ipad block first (HmacSha256.cpp:24-29)
+        else sha256_init(st);
         for (uint32_t t = 0; t < nint; ++t) {
             if (t >= 2 && t <= Ts + 1) {
                 const uint32_t u = t - 2;
@@ -358,7 +298,7 @@ __global__ __launch_bounds__(kSWaves * kSRec) void duplex_split_kernel(DuplexPar
             } else if (t == Ts + 2 && live) {
                 uint32_t d[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // digest as LE words of its bytes
                 if (valid) {
-                    const uint32_t nb = (r + 9u + 63u) >> 6;
+                    const uint32_t nb = sha256_tail_blocks(r);
 #pragma unroll
                     for (int k = 0; k < 3; ++k) {
                         if ((uint32_t)k < nb) {
@@ -372,46 +312,20 @@ __global__ __launch_bounds__(kSWaves * kSRec) void duplex_split_kernel(DuplexPar
                         }
                     }
                     if (kAead) {  // HMAC outer (HmacSha256.cpp:31-38)
-                        uint32_t inner[8], x[16];
+                        uint32_t inner[8];
 #pragma unroll
                         for (int i = 0; i < 8; ++i) inner[i] = st[i];
-#pragma unroll
-                        for (int i = 0; i < 8; ++i) st[i] = kShaIV[i];
-#pragma unroll
-                        for (int i = 0; i < 16; ++i) x[i] = (i < 8 ? kb[i] : 0u) ^ 0x5c5c5c5cu;
-                        sha256_compress(st, x);
-#pragma unroll
-                        for (int i = 0; i < 8; ++i) x[i] = inner[i];
-                        x[8] = 0x80000000u;
-#pragma unroll
-                        for (int i = 9; i < 15; ++i) x[i] = 0u;
-                        x[15] = (64 + 32) * 8;
-                        sha256_compress(st, x);
+                        hmac_key_state(st, kb, kHmacOpad);
+                        hmac_outer_finish(st, inner);
                     }
 #pragma unroll
                     for (int i = 0; i < 8; ++i) d[i] = bswap32(st[i]);
                 }
-                if (!OPEN) {
-                    if (valid) {
-                        uint8_t* dp = (KIND == DK_CHUNK ? p.digests : p.macs) + 32ull * rec;
-                        reinterpret_cast<uint4*>(dp)[0] = make_uint4(d[0], d[1], d[2], d[3]);
-                        reinterpret_cast<uint4*>(dp)[1] = make_uint4(d[4], d[5], d[6], d[7]);
-                    } else {
-                        sp_zero_bytes(p.out + ob, Lo);  // not processed
-                    }
-                } else {
-                    uint32_t diff = valid ? 0u : 1u;
-                    if (valid) {
-                        const uint8_t* ep = (KIND == DK_CHUNK ? p.expect : p.macs_in) + 32ull * rec;
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) diff |= ld32(ep + 4 * j) ^ d[j];
-                        if (kAead && runs[(Ts + 1u) & 1u][0][lane].x == 0u) diff = 1;
-                    }
-                    p.ok[rec] = diff == 0u ? 1 : 0;
-                    if (diff != 0u) sp_zero_bytes(p.out + ob, Lo);  // no plaintext for a failed record
-                }
+                const bool tag_bad = kAead && OPEN && valid && runs[(Ts + 1u) & 1u][0][lane].x == 0u;
+                finish_record<OPEN>(p, g, d, OPEN ? nullptr : (KIND == DK_CHUNK ? p.digests : p.macs) + 32ull * rec,
+                                    OPEN ? (KIND == DK_CHUNK ? p.expect : p.macs_in) + 32ull * rec : nullptr, tag_bad);
             }
-            ENET_SP_BARRIER();
+            ENET_DX_BARRIER();
         }
     }
 }

@@ -482,6 +482,93 @@ __device__ __forceinline__ void sha256_compress(uint32_t st[8], uint32_t w[16]) 
     st[4] += e; st[5] += f; st[6] += g; st[7] += h;
 }
 
+__device__ __forceinline__ void sha256_init(uint32_t st[8]) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) st[i] = kShaIV[i];
+}
+
+// count_leading_zero_bits of a digest held as big-endian words (256 for the zero digest)
+__device__ __forceinline__ uint32_t digest_leading_zero_bits(const uint32_t st[8]) {
+    uint32_t total = 0;
+    bool open = true;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const uint32_t z = st[j] == 0u ? 32u : (uint32_t)__builtin_clz(st[j]);
+        total += open ? z : 0u;
+        open = open && st[j] == 0u;
+    }
+    return total;
+}
+
+// Block k of the 1-3 padded final blocks (sha256_tail_blocks(r) of them) of a message whose
+// ragged end is r < 128 bytes (Sha256.cpp:94-126): message tail, 0x80, zeros, and in the last
+// block the BE64 bit length `bits` of the whole message.  tail = the ragged end as 32
+// little-endian words; block k reads words [16 k, 16 k + 16) of it (block 2 none), and what
+// lies at or past byte r is masked.
+__device__ __forceinline__ uint32_t sha256_tail_blocks(uint32_t r) { return (r + 9u + 63u) >> 6; }
+__device__ __forceinline__ void sha256_tail_block(int k, const uint32_t tail[32], uint32_t r, uint64_t bits,
+                                                  uint32_t x[16]) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const uint32_t b = 64u * k + 4u * i;
+        const uint32_t v = k < 2 ? bswap32(tail[16 * k + i]) : 0u;
+        const uint32_t m = b + 4u <= r ? 0xffffffffu : (b >= r ? 0u : 0xffffffffu << (8u * (4u - (r - b))));
+        x[i] = (v & m) | ((r >> 2) == (b >> 2) ? 0x80000000u >> (8u * (r & 3u)) : 0u);
+    }
+    if ((uint32_t)k == sha256_tail_blocks(r) - 1u) {
+        x[14] = (uint32_t)(bits >> 32);
+        x[15] = (uint32_t)bits;
+    }
+}
+
+// ---- HMAC-SHA256 (HmacSha256.cpp:11-39) on big-endian words, everything in registers
+constexpr uint32_t kHmacIpad = 0x36363636u, kHmacOpad = 0x5c5c5c5cu;
+
+// st = the state after the key block ^ pad: kb is the key as KW words (8: a 32-byte key, the
+// block is key || 0^32; 16: a whole key block)
+template <int KW>
+__device__ __forceinline__ void hmac_key_state(uint32_t st[8], const uint32_t (&kb)[KW], uint32_t pad) {
+    static_assert(KW == 8 || KW == 16, "a 32-byte key or a whole key block");
+    uint32_t w[16];
+    sha256_init(st);
+#pragma unroll
+    for (int j = 0; j < 16; ++j) w[j] = (j < KW ? kb[j] : 0u) ^ pad;
+    sha256_compress(st, w);
+}
+
+// st_outer (after the opad block) absorbs the second block of the 96-byte outer message:
+// inner digest || 0x80 || 0... || BE64(96 * 8)
+__device__ __forceinline__ void hmac_outer_finish(uint32_t st_outer[8], const uint32_t inner[8]) {
+    uint32_t w[16];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) w[j] = inner[j];
+    w[8] = 0x80000000u;
+#pragma unroll
+    for (int j = 9; j < 15; ++j) w[j] = 0u;
+    w[15] = (64 + 32) * 8;
+    sha256_compress(st_outer, w);
+}
+
+// HMAC with a 32-byte key over NW message words (NW <= 13: one inner block).  Four compressions.
+template <int NW>
+__device__ __forceinline__ void hmac32_short(const uint32_t (&kb)[8], const uint32_t (&m)[NW], uint32_t out[8]) {
+    static_assert(NW <= 13, "the message and its padding share one block");
+    uint32_t st[8], w[16];
+    hmac_key_state(st, kb, kHmacIpad);
+#pragma unroll
+    for (int j = 0; j < 15; ++j) w[j] = j < NW ? m[j] : (j == NW ? 0x80000000u : 0u);
+    w[15] = (64 + 4 * NW) * 8;
+    sha256_compress(st, w);
+    hmac_key_state(out, kb, kHmacOpad);
+    hmac_outer_finish(out, st);
+}
+
+// the enet_hmac_midstates layout for one 32-byte key: inner state at mid[0..8), outer at mid[8..16)
+__device__ __forceinline__ void hmac_midstates(const uint32_t (&kb)[8], uint32_t mid[16]) {
+    hmac_key_state(mid, kb, kHmacIpad);
+    hmac_key_state(mid + 8, kb, kHmacOpad);
+}
+
 // ----------------------------------------------------------------------------- byte I/O
 // Bytes [off, off + 4M) of the little-endian byte string in[0..4N) as M words, zero past the
 // end (off <= 4N).  The per-lane word offset goes through a log2(N)-stage barrel shift over

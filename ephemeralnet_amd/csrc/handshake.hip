@@ -24,11 +24,6 @@ namespace {
 constexpr uint32_t kDhPrime = 2147483647u;  // KeyExchange::kPrime = 2^31 - 1
 constexpr uint32_t kDhGenerator = 5u;       // KeyExchange::kGenerator
 
-__device__ __forceinline__ void hs_sha_init(uint32_t st[8]) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) st[i] = kShaIV[i];
-}
-
 // a * b mod 2^31-1 for a, b < 2^31-1, exact: 2^31 == 1, so the 62-bit product folds twice
 // (first sum < 2^32, second <= P + 1) and one conditional subtraction finishes it.
 __device__ __forceinline__ uint32_t mulmod_p(uint32_t a, uint32_t b) {
@@ -66,26 +61,28 @@ __device__ __forceinline__ void shared_secret(uint32_t scalar, uint32_t secret[8
 #pragma unroll
     for (int j = 2; j < 15; ++j) w[j] = 0u;
     w[15] = 4 * 8;
-    hs_sha_init(secret);
+    sha256_init(secret);
     sha256_compress(secret, w);
 }
 
-// HMAC-SHA256 with a 32-byte key (big-endian words kb) over NW message words (NW <= 13: one
-// inner block), HmacSha256.cpp:11-39.  Four compressions.
+// The shared hmac32_short / hmac_midstates (enet_device.hpp), written out over one w[16].  These
+// two kernels run one wave per SIMD, so their time is one wave's instruction schedule: built from
+// the shared pieces, the same 8 198 instructions were allocated 93 VGPRs instead of 130 and ran
+// 1.5-3 % slower (accept 32.2 -> 32.7 us, rotate 18.8 -> 19.4 us, profiles/hash_vocab_ab.jsonl).
 template <int NW>
-__device__ __forceinline__ void hmac32_short(const uint32_t kb[8], const uint32_t m[NW], uint32_t out[8]) {
+__device__ __forceinline__ void hs_hmac32_short(const uint32_t kb[8], const uint32_t m[NW], uint32_t out[8]) {
     uint32_t st[8], w[16];
-    hs_sha_init(st);
+    sha256_init(st);
 #pragma unroll
-    for (int j = 0; j < 16; ++j) w[j] = (j < 8 ? kb[j] : 0u) ^ 0x36363636u;
+    for (int j = 0; j < 16; ++j) w[j] = (j < 8 ? kb[j] : 0u) ^ kHmacIpad;
     sha256_compress(st, w);
 #pragma unroll
     for (int j = 0; j < 15; ++j) w[j] = j < NW ? m[j] : (j == NW ? 0x80000000u : 0u);
     w[15] = (64 + 4 * NW) * 8;
     sha256_compress(st, w);
-    hs_sha_init(out);
+    sha256_init(out);
 #pragma unroll
-    for (int j = 0; j < 16; ++j) w[j] = (j < 8 ? kb[j] : 0u) ^ 0x5c5c5c5cu;
+    for (int j = 0; j < 16; ++j) w[j] = (j < 8 ? kb[j] : 0u) ^ kHmacOpad;
     sha256_compress(out, w);
 #pragma unroll
     for (int j = 0; j < 8; ++j) w[j] = st[j];
@@ -100,9 +97,9 @@ __device__ __forceinline__ void hmac32_short(const uint32_t kb[8], const uint32_
 __device__ __forceinline__ void store_midstates(const uint32_t kb[8], uint32_t* __restrict__ mid) {
 #pragma unroll
     for (int pass = 0; pass < 2; ++pass) {
-        const uint32_t pad = pass == 0 ? 0x36363636u : 0x5c5c5c5cu;
+        const uint32_t pad = pass == 0 ? kHmacIpad : kHmacOpad;
         uint32_t st[8], w[16];
-        hs_sha_init(st);
+        sha256_init(st);
 #pragma unroll
         for (int j = 0; j < 16; ++j) w[j] = (j < 8 ? kb[j] : 0u) ^ pad;
         sha256_compress(st, w);
@@ -116,19 +113,6 @@ __device__ __forceinline__ void store_row(uint8_t* __restrict__ row, const uint3
     uint32_t* o = reinterpret_cast<uint32_t*>(row);
 #pragma unroll
     for (int j = 0; j < 8; ++j) o[j] = bswap32(v[j]);
-}
-
-// count_leading_zero_bits of a digest held as big-endian words (256 for the zero digest)
-__device__ __forceinline__ uint32_t leading_zero_bits(const uint32_t st[8]) {
-    uint32_t total = 0;
-    bool open = true;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const uint32_t z = st[j] == 0u ? 32u : (uint32_t)__builtin_clz(st[j]);
-        total += open ? z : 0u;
-        open = open && st[j] == 0u;
-    }
-    return total;
 }
 
 }  // namespace
@@ -153,7 +137,7 @@ __global__ __launch_bounds__(kWG) void handshake_accept_kernel(HandshakeParams P
         w[10] = 0u; w[11] = 32u;
 #pragma unroll
         for (int j = 0; j < 4; ++j) w[12 + j] = bswap32(lid[j]);
-        hs_sha_init(st);
+        sha256_init(st);
         sha256_compress(st, w);
 #pragma unroll
         for (int j = 0; j < 4; ++j) w[j] = bswap32(lid[4 + j]);
@@ -164,7 +148,7 @@ __global__ __launch_bounds__(kWG) void handshake_accept_kernel(HandshakeParams P
         for (int j = 9; j < 15; ++j) w[j] = 0u;
         w[15] = 96 * 8;
         sha256_compress(st, w);
-        if (leading_zero_bits(st) < P.difficulty) {
+        if (digest_leading_zero_bits(st) < P.difficulty) {
             P.verdict[i] = ENET_DEV_HS_BAD_POW;
             return;
         }
@@ -178,7 +162,7 @@ __global__ __launch_bounds__(kWG) void handshake_accept_kernel(HandshakeParams P
     shared_secret(modexp_p(reduce_p(remote), P.local_private), secret);
     const uint32_t material[2] = {remote < P.local_public ? remote : P.local_public,
                                   remote < P.local_public ? P.local_public : remote};
-    hmac32_short<2>(secret, material, key);
+    hs_hmac32_short<2>(secret, material, key);
     store_row(P.table.secrets + 32ull * slot, secret);
     store_row(P.table.keys + 32ull * slot, key);
     store_midstates(key, P.table.mid + 16ull * slot);
@@ -206,7 +190,7 @@ __global__ __launch_bounds__(kWG) void session_rotate_kernel(SessionTableParams 
     for (int j = 0; j < 8; ++j) secret[j] = bswap32(sp[j]);
     const uint32_t material[4] = {(uint32_t)(c >> 32), (uint32_t)c, (uint32_t)((uint64_t)now >> 32),
                                   (uint32_t)(uint64_t)now};
-    hmac32_short<4>(secret, material, key);
+    hs_hmac32_short<4>(secret, material, key);
     T.counters[s] = c;
     T.last_rotation[s] = now;
     store_row(T.keys + 32ull * s, key);

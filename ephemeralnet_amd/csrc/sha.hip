@@ -54,11 +54,6 @@ __device__ __forceinline__ void sha_absorb_final(uint32_t st[8], const uint8_t* 
     sha256_compress(st, w);
 }
 
-__device__ __forceinline__ void sha_init(uint32_t st[8]) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) st[i] = kShaIV[i];
-}
-
 __global__ __launch_bounds__(kWG) void sha_kernel(ShaParams p) {
     const uint32_t gid = blockIdx.x * kWG + threadIdx.x;
     if (gid >= p.n) return;
@@ -69,7 +64,7 @@ __global__ __launch_bounds__(kWG) void sha_kernel(ShaParams p) {
     uint32_t st[8];
 
     if (!p.keys) {  // plain SHA-256 (Sha256::digest)
-        sha_init(st);
+        sha256_init(st);
         sha_absorb_final(st, msg, len, 0);
     } else {  // HMAC-SHA256
         const uint8_t* kp;
@@ -84,7 +79,7 @@ __global__ __launch_bounds__(kWG) void sha_kernel(ShaParams p) {
         uint32_t kb[16];  // key block as big-endian words
         if (klen > 64) {
             uint32_t hk[8];
-            sha_init(hk);
+            sha256_init(hk);
             sha_absorb_final(hk, kp, klen, 0);
 #pragma unroll
             for (int i = 0; i < 8; ++i) { kb[i] = hk[i]; kb[8 + i] = 0; }
@@ -100,28 +95,12 @@ __global__ __launch_bounds__(kWG) void sha_kernel(ShaParams p) {
                 kb[i] = v;
             }
         }
-        uint32_t w[16];
-        // inner = SHA(ipad || msg)
-        sha_init(st);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) w[i] = kb[i] ^ 0x36363636u;
-        sha256_compress(st, w);
-        sha_absorb_final(st, msg, len, 64);
-        // outer = SHA(opad || inner)
+        // inner = SHA(ipad || msg), outer = SHA(opad || inner)
         uint32_t inner[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) inner[i] = st[i];
-        sha_init(st);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) w[i] = kb[i] ^ 0x5c5c5c5cu;
-        sha256_compress(st, w);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) w[i] = inner[i];
-        w[8] = 0x80000000u;
-#pragma unroll
-        for (int i = 9; i < 15; ++i) w[i] = 0;
-        w[15] = (64 + 32) * 8;
-        sha256_compress(st, w);
+        hmac_key_state(inner, kb, kHmacIpad);
+        sha_absorb_final(inner, msg, len, 64);
+        hmac_key_state(st, kb, kHmacOpad);
+        hmac_outer_finish(st, inner);
     }
 
     if (p.expect) {  // verify (HmacSha256::verify): OR-accumulate the difference
@@ -170,8 +149,8 @@ hipError_t launch_sha(const ShaParams& p, hipStream_t s) {
 }
 
 // KeyManager::derive_key (src/network/KeyManager.cpp:74-92): HMAC-SHA256 with the 32-byte shared
-// secret over the 16-byte material BE64(counter) || BE64(ticks) -- four compressions per
-// session (ipad, inner message, opad, outer), one session per lane.
+// secret over the 16-byte material BE64(counter) || BE64(ticks) -- hmac32_short<4>, one
+// session per lane.
 __global__ __launch_bounds__(kWG) void session_key_kernel(uint32_t n, const uint8_t* __restrict__ secrets,
                                                           const uint64_t* __restrict__ counters,
                                                           const int64_t* __restrict__ ticks,
@@ -183,31 +162,9 @@ __global__ __launch_bounds__(kWG) void session_key_kernel(uint32_t n, const uint
     const uint32_t kb[8] = {bswap32(k0.x), bswap32(k0.y), bswap32(k0.z), bswap32(k0.w),
                             bswap32(k1.x), bswap32(k1.y), bswap32(k1.z), bswap32(k1.w)};
     const uint64_t c = counters[i], t = (uint64_t)ticks[i];
-    uint32_t st[8], w[16];
-    sha_init(st);
-#pragma unroll
-    for (int j = 0; j < 16; ++j) w[j] = (j < 8 ? kb[j] : 0u) ^ 0x36363636u;
-    sha256_compress(st, w);
-    w[0] = (uint32_t)(c >> 32); w[1] = (uint32_t)c; w[2] = (uint32_t)(t >> 32); w[3] = (uint32_t)t;
-    w[4] = 0x80000000u;
-#pragma unroll
-    for (int j = 5; j < 15; ++j) w[j] = 0u;
-    w[15] = (64 + 16) * 8;
-    sha256_compress(st, w);
-    uint32_t inner[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) inner[j] = st[j];
-    sha_init(st);
-#pragma unroll
-    for (int j = 0; j < 16; ++j) w[j] = (j < 8 ? kb[j] : 0u) ^ 0x5c5c5c5cu;
-    sha256_compress(st, w);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) w[j] = inner[j];
-    w[8] = 0x80000000u;
-#pragma unroll
-    for (int j = 9; j < 15; ++j) w[j] = 0u;
-    w[15] = (64 + 32) * 8;
-    sha256_compress(st, w);
+    const uint32_t material[4] = {(uint32_t)(c >> 32), (uint32_t)c, (uint32_t)(t >> 32), (uint32_t)t};
+    uint32_t st[8];
+    hmac32_short<4>(kb, material, st);
     uint4* o = reinterpret_cast<uint4*>(out + 32ull * i);
     o[0] = make_uint4(bswap32(st[0]), bswap32(st[1]), bswap32(st[2]), bswap32(st[3]));
     o[1] = make_uint4(bswap32(st[4]), bswap32(st[5]), bswap32(st[6]), bswap32(st[7]));
@@ -224,18 +181,11 @@ __global__ __launch_bounds__(kWG) void hmac_midstate_kernel(uint32_t n, const ui
     uint32_t kb[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) kb[j] = bswap32(kp[j]);
+    uint32_t m[16];
+    hmac_midstates(kb, m);
     uint32_t* o = mid + 16ull * i;
 #pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-        const uint32_t pad = pass == 0 ? 0x36363636u : 0x5c5c5c5cu;
-        uint32_t st[8], w[16];
-        sha_init(st);
-#pragma unroll
-        for (int j = 0; j < 16; ++j) w[j] = (j < 8 ? kb[j] : 0u) ^ pad;
-        sha256_compress(st, w);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) o[8 * pass + j] = st[j];
-    }
+    for (int j = 0; j < 16; ++j) o[j] = m[j];
 }
 
 hipError_t launch_hmac_midstates(uint32_t n, const uint8_t* keys, uint32_t* mid, hipStream_t s) {

@@ -86,10 +86,14 @@ def both_paths(enet, fn):
 @pytest.mark.parametrize("hdr", [16, 0])
 @pytest.mark.parametrize("L,n,base", [(1500, 600, 0), (1452, 300, 3), (100, 513, 1), (1, 260, 0),
                                       (0, 257, 2), (127, 256, 0), (129, 300, 7), (1535, 260, 0),
-                                      (1408, 256, 5), (4096, 300, 0), (96, 300, 0), (97, 256, 0)])
+                                      (1408, 256, 5), (4096, 300, 0), (96, 300, 0), (97, 256, 0),
+                                      (55, 130, 0), (56, 130, 0), (119, 130, 0), (120, 130, 0)])
 def test_ragged_frames_vs_oracle(enet, hdr, L, n, base):
     """Uniform batches whose length is not a multiple of 128 B (the MTU case):
-    seal = oracle, open round-trips with ok = 1 and the decrypted MACs, two-pass agrees."""
+    seal = oracle, open round-trips with ok = 1 and the decrypted MACs, two-pass agrees.  55 / 56
+    and 119 / 120 are where HMAC's inner padding moves from one to two final blocks, without and
+    with the MAC crossing the 128-byte slot boundary (n = 130: two 64-record workgroups and a
+    partial one)."""
     msgs = [splitmix_bytes(17000 + 7 * L + i, L) for i in range(n)]
     keys = [splitmix_bytes(18000 + i, 32) for i in range(n)]
     nonces = [splitmix_bytes(19000 + i, 12) for i in range(n)]
@@ -389,21 +393,24 @@ def test_aead_hmac_c5_mixed_vs_oracle(enet, split, sort):
             assert ok[i] == 1 and got[i] == items[i], i
 
 
-# every ragged-end shape of the split kernel: tail 0..127 bytes (1, 2 or 3 final SHA-256 blocks:
-# r + 9 <= 64, <= 128, > 128), whole stages, empty records, a record of the wrong output size
+# every ragged-end shape of both duplex kernels (they share the final-block builder): tail 0..127
+# bytes (1, 2 or 3 final SHA-256 blocks: r + 9 <= 64, <= 128, > 128), whole stages, empty records,
+# a record of the wrong output size
 EDGE_LENS = [0, 1, 15, 16, 55, 56, 63, 64, 65, 119, 120, 127, 128, 129, 183, 184, 191, 192, 255, 256,
              257, 383, 1000, 1500, 4095, 4096, 16384, 20000 + 37, 65536]
 
 
+@pytest.mark.parametrize("split", [1, 0])
 @pytest.mark.parametrize("kind", ["chunk", "aeadh"])
 @pytest.mark.parametrize("base", [0, 3])
-def test_split_kernel_edge_lengths_vs_oracle(enet, kind, base):
-    """duplex_split.hip forced on: bit-exact ciphertext, SHA-256 / HMAC and Poly1305 tags for
-    every tail shape, in-order and reversed (caller order); open verifies and rejects a flipped
-    last byte per record shape; a record whose output range is the wrong size is zeroed (ok 0)."""
+def test_duplex_kernels_edge_lengths_vs_oracle(enet, kind, base, split):
+    """duplex_split.hip forced on (split 1) or off (0: duplex.hip's chunk / AEAD + HMAC kinds):
+    bit-exact ciphertext, SHA-256 / HMAC and Poly1305 tags for every tail shape, in-order and
+    reversed (caller order); open verifies and rejects a flipped last byte per record shape; a
+    record whose output range is the wrong size is zeroed (ok 0)."""
     import hashlib
     import torch
-    enet.set_duplex_split(1)
+    enet.set_duplex_split(split)
     try:
         lens = EDGE_LENS * 3
         n = len(lens)
