@@ -262,6 +262,8 @@ class Batch:
 
     arena: uint8 [total]; offsets: int64 [n+1]; keys: uint8 [n,32] (or [1,32] with
     key_stride=0); nonces: uint8 [n,12].  `out`/`out_offsets` default to a same-shape arena.
+    count: how many records the call processes when `order` (int32 [count]) names a subset of
+    the batch; None = all n.
     """
     arena: "object"
     offsets: "object"
@@ -271,6 +273,7 @@ class Batch:
     order: "object" = None
     total_bytes_hint: int = 0
     max_len_hint: int = 0
+    count: Optional[int] = None
 
     @property
     def n(self) -> int:
@@ -278,7 +281,7 @@ class Batch:
 
     def records(self, out, out_offsets) -> _Records:
         r = _Records()
-        r.count = self.n
+        r.count = self.n if self.count is None else self.count
         r.in_offsets = _ptr(self.offsets)
         r.out_offsets = _ptr(out_offsets)
         r.in_ = _ptr(self.arena)

@@ -436,7 +436,7 @@ int chunk_store_host_hash(const enet_records* r, const uint8_t* ids, uint8_t* ha
         enet::RecParams p = rec_params(&q);
         p.counters = reinterpret_cast<const uint32_t*>(ids ? ids : hashes);
         p.counter_stride = 8;
-        rc = run_records(enet::MODE_XOR, &q, p, st, "chunk_store long chacha", r->count);
+        rc = run_records(enet::MODE_XOR, &q, p, st, "chunk_store long chacha");
     }
     g_hh_batches.fetch_add(1, std::memory_order_relaxed);
     return chunk_finish(cs, st, rc);
@@ -456,7 +456,7 @@ int chunk_fetch_host_hash(const enet_records* r, const uint8_t* ids, const uint8
         enet::RecParams p = rec_params(&q);
         p.counters = reinterpret_cast<const uint32_t*>(ids);
         p.counter_stride = 8;
-        rc = run_records(enet::MODE_XOR, &q, p, st, "chunk_fetch long chacha", n);
+        rc = run_records(enet::MODE_XOR, &q, p, st, "chunk_fetch long chacha");
     }
     // the expected hashes to the host, then the plaintext in pieces as the host hashes it
     std::vector<uint8_t> want(32ull * n);

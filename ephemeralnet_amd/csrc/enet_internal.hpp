@@ -6,7 +6,7 @@
 
 #include <string>
 
-#include "long_route.hpp"  // kMaxLanesPerRecord, RecMode, kSegMin, kSegTileBytes
+#include "long_route.hpp"  // kMaxLanesPerRecord, RecMode, kSegMin, kSegTileBytes, SegEntry
 
 namespace enet {
 
@@ -52,8 +52,9 @@ struct RecParams {
     // nonce(12) || BE32(|body|) (SessionManager.cpp:376-387).  Seal writes it in front of the
     // body; open reads the nonce from it.
     uint32_t hdr;
-    // records the sequence-parallel path (segments.hip) claimed: skip[rec] != 0 -> not this
-    // kernel's record (nullable; per-lane path only)
+    // records the sequence-parallel path (segments.hip) claimed: skip[pos] != 0 -> the record at
+    // position pos of the launch is not this kernel's (nullable; [n] bytes; set only for one
+    // per-lane launch over the whole batch, rec_base == 0)
     const uint8_t* skip;
 };
 
@@ -201,13 +202,7 @@ hipError_t launch_shamir_combine(uint32_t n, uint32_t threshold, const uint8_t* 
                                  uint8_t* secrets_out, uint8_t* ok, hipStream_t s);
 
 // ---- sequence-parallel path for long records (segments.hip)
-// A claimed record's entry; entries are sorted by tile_base (claimed by CAS on one packed word).
-struct SegEntry {
-    uint32_t rec, tile_base, ntiles, arrived;
-    uint32_t aad_len, nbits, pad0, pad1;
-    uint32_t r[4], s[4];     // AEAD: one-time key halves (r unclamped words; s the pad)
-    uint32_t pw[5 * 40];     // AEAD: r^(2^k) in 26-bit limbs, k < nbits
-};
+// (SegEntry, a claimed record's entry, is in long_route.hpp beside the scratch layout)
 constexpr uint64_t kSegMaxLen = 1ull << 35;  // 32-bit Poly1305 block positions inside a record
 struct SegParams {
     int mode;                  // MODE_XOR / MODE_SEAL / MODE_OPEN
@@ -230,7 +225,9 @@ struct SegParams {
     // scratch (stream-ordered, long_records.cpp seg_begin)
     unsigned long long* hdr;   // count << 40 | tiles claimed
     SegEntry* entries;         // [entry_cap]
-    uint8_t* claimed;          // [index bound]: indexed by record
+    uint8_t* claimed;          // [n]: claimed[pos] != 0 -> the record at position pos of the launch
+                               // (order[pos], or pos) is the tiles'; indexed by POSITION, so n
+                               // bytes hold it whatever indices the order names
     uint32_t* partials;        // [tile_cap][8]
     uint32_t entry_cap, tile_cap;
     uint64_t long_min;

@@ -119,33 +119,31 @@ int run_uniform_aead(int mode, const enet_records* r, const RecParams& p, hipStr
 }
 
 // Plan + tile kernels for the batch's long records; p.skip marks them for the record engine.
-int seg_begin(int mode, const enet_records* r, RecParams& p, uint64_t long_min, hipStream_t st, uint32_t index_n) {
+int seg_begin(int mode, const enet_records* r, RecParams& p, uint64_t long_min, hipStream_t st) {
     const uint32_t n = r->count;
-    const uint64_t total = r->total_bytes_hint ? r->total_bytes_hint
-                                               : (uint64_t)std::min<uint32_t>(n, 1024u) * r->max_len_hint;
-    // capacities from the hints; records past them stay with the record engine (never wrong bytes)
-    const uint64_t ecap = std::min<uint64_t>(n, long_min ? total / long_min + 1 : n);
-    const uint64_t tcap = std::min<uint64_t>(total / kSegTileBytes + ecap + 1, 0xFFFFFFFFull);
-    const size_t o_ent = 256, o_cl = o_ent + (size_t)ecap * sizeof(SegEntry),
-                 o_part = (o_cl + index_n + 255) & ~size_t(255), bytes = o_part + (size_t)tcap * 32;
+    // capacities from the hints, one claim byte per position of the launch (long_route.hpp)
+    const SegLayout lay = seg_layout(n, r->max_len_hint, r->total_bytes_hint, long_min);
     std::unique_lock<std::mutex> lk;
     StreamScratch* s = nullptr;
     if (int e = scratch_of(st, lk, s)) return e;
-    if (int e = grow(s->plan, bytes, 256u << 10, false, st, "sequence-parallel scratch", "sequence-parallel scratch")) return e;
+    if (int e = grow(s->plan, (size_t)lay.bytes, 256u << 10, false, st, "sequence-parallel scratch", "sequence-parallel scratch")) return e;
     uint8_t* base = static_cast<uint8_t*>(s->plan.ptr);
     lk.unlock();
     SegParams q = seg_params(mode, p);
     q.hdr = reinterpret_cast<unsigned long long*>(base);
-    q.entries = reinterpret_cast<SegEntry*>(base + o_ent);
-    q.claimed = base + o_cl;
-    q.partials = reinterpret_cast<uint32_t*>(base + o_part);
-    q.entry_cap = (uint32_t)ecap;
-    q.tile_cap = (uint32_t)tcap;
+    q.entries = reinterpret_cast<SegEntry*>(base + lay.o_ent);
+    q.claimed = base + lay.o_cl;
+    q.partials = reinterpret_cast<uint32_t*>(base + lay.o_part);
+    q.entry_cap = (uint32_t)lay.ecap;
+    q.tile_cap = (uint32_t)lay.tcap;
     q.long_min = long_min;
     const uint32_t plan_blocks = (uint32_t)std::min<uint64_t>((n + 255) / 256, 1024);
-    const uint32_t tile_blocks = (uint32_t)std::min<uint64_t>(tcap, 4096);
+    const uint32_t tile_blocks = (uint32_t)std::min<uint64_t>(lay.tcap, 4096);
     p.skip = q.claimed;
-    p.uniform_len = 0;  // per-lane path: the staged paths assume every record is theirs
+    // per-lane path: the staged paths assume every record is theirs.  It also makes the record
+    // engine ONE launch over positions 0 .. n-1 (rec_base == 0), which is what lets the plan
+    // kernel and records_body agree on claimed[position]
+    p.uniform_len = 0;
     g_seg_batches.fetch_add(1, std::memory_order_relaxed);
     return hip_status(launch_seg(q, plan_blocks, tile_blocks, st), "sequence-parallel launch");
 }
@@ -178,7 +176,7 @@ hipMemPool_t scratch_pool() {
     return pools[dev];
 }
 
-int run_records(int mode, const enet_records* r, RecParams& p, hipStream_t st, const char* what, uint32_t index_n) {
+int run_records(int mode, const enet_records* r, RecParams& p, hipStream_t st, const char* what) {
     const RouteChoice c = choose_long_route(mode, r->order != nullptr, r->count, r->max_len_hint,
                                             r->total_bytes_hint, g_seg_min.load(std::memory_order_relaxed));
     switch (c.route) {
@@ -188,7 +186,7 @@ int run_records(int mode, const enet_records* r, RecParams& p, hipStream_t st, c
     case LongRoute::UniformAead:
         return run_uniform_aead(mode, r, p, st, what);
     case LongRoute::PlanTiles:
-        if (int e = seg_begin(mode, r, p, c.long_min, st, index_n ? index_n : r->count)) return e;
+        if (int e = seg_begin(mode, r, p, c.long_min, st)) return e;
         break;
     case LongRoute::RecordEngine: break;
     }

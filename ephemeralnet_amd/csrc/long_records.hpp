@@ -19,9 +19,9 @@ void set_seg_min(int64_t bytes);  // enet_set_seg_min, argument checked
 uint64_t seg_batches();           // enet_seg_batches
 
 // The record engine over the batch, with its long records on the tiles first where
-// choose_long_route wants them.  index_n: one past the largest record index (r->count unless
-// r->order names a subset).
-int run_records(int mode, const enet_records* r, RecParams& p, hipStream_t st, const char* what,
-                uint32_t index_n = 0);
+// choose_long_route wants them.  r->order may name any r->count records of a larger batch: the
+// tiles' claim bytes are kept per position of the launch, not per record index, so no bound on
+// the indices is needed (or known: the order is device memory, and this call does not synchronise).
+int run_records(int mode, const enet_records* r, RecParams& p, hipStream_t st, const char* what);
 
 }  // namespace enet

@@ -134,8 +134,11 @@ __device__ __forceinline__ void records_body(const RecParams& p) {
     const uint32_t rec = in_batch ? (p.order ? p.order[group] : group + p.rec_base) : 0u;
     // a record the sequence-parallel path claimed (segments.hip) is not this kernel's -- except
     // that an open whose tag failed there is zeroed here (the launch boundary orders these zero
-    // stores after every tile's plaintext stores; no plaintext of a failed record is released)
-    const bool claimed = COOP == 0 && in_batch && p.skip && p.skip[rec];
+    // stores after every tile's plaintext stores; no plaintext of a failed record is released).
+    // skip is indexed by the record's position in the launch, as seg_plan_kernel wrote it: the
+    // host sets skip only with uniform_len == 0, i.e. for one per-lane launch over the whole
+    // batch (rec_base == 0), so group IS that position -- with or without an order.
+    const bool claimed = COOP == 0 && in_batch && p.skip && p.skip[seg_claim_slot(group, rec)];
     if (MODE == MODE_OPEN && claimed && p.ok[rec] == 0) {
         const uint64_t a = p.out_off[rec], L = p.in_off[rec + 1] - p.in_off[rec];
         const uint32_t j0 = (blockIdx.x * WGS + threadIdx.x) & (P - 1);

@@ -13,7 +13,8 @@
 //   1. seg_plan_kernel: every record >= the threshold CLAIMS a contiguous range of tile indices
 //      (one 64-bit CAS on a packed count|tiles word, so entries come out sorted by tile base) and
 //      writes its entry -- for the AEAD also the one-time Poly1305 key and the power table
-//      r^(2^k), k = 0..nbits -- and a claimed[] byte per record that the record engine skips.
+//      r^(2^k), k = 0..nbits -- and, per position of the launch, a claimed[] byte that makes
+//      the record engine skip the record.
 //   2. seg_kernel: a grid of 256-lane workgroups walks the tiles.  Lane j of a tile owns the four
 //      ChaCha20 blocks [tile*1024 + 4j, +4) of its record; a tile whose 64 KiB are all whole blocks
 //      moves them through a wave-private LDS slab with whole 128-byte lines per load / store
@@ -221,7 +222,9 @@ __global__ __launch_bounds__(kSegThreads) void seg_plan_kernel(SegParams p) {
                 }
             }
         }
-        if (p.claimed) p.claimed[i] = claim ? 1 : 0;
+        // by position, not by record: [n] bytes whatever indices the order names (records_body
+        // reads skip[group], the same position: its launch covers positions 0 .. n-1)
+        if (p.claimed) p.claimed[seg_claim_slot(pos, i)] = claim ? 1 : 0;
         if (!claim) continue;
         SegEntry& e = p.entries[idx];
         e.rec = i;

@@ -57,7 +57,10 @@ typedef struct enet_records {
     const uint32_t* order;      /* optional [count] record indices to process, in this order
                                    (e.g. longest first, or one length class of a larger batch);
                                    NULL = 0..count-1.  Indices address offsets/keys/nonces/tags/ok
-                                   of the full batch, so results stay position-indexed. */
+                                   of the full batch, so results stay position-indexed; an index
+                                   may be >= count, and records the order does not name are left
+                                   untouched.  With a subset the two hints below describe the
+                                   NAMED records: their sum and their maximum. */
     uint64_t total_bytes_hint;  /* host-known sum of input lengths, 0 = unknown (scheduling) */
     uint32_t max_len_hint;      /* host-known max record length, 0 = unknown (scheduling) */
     /* The hints only choose kernels and launch shapes.  total == count * max declares a uniform

@@ -1,5 +1,6 @@
-// The routing rule for long records (csrc/long_route.hpp choose_long_route) against a table
-// worked out by hand from the rule: host C++ only, exit status 0 when every row agrees.
+// The routing rule for long records (csrc/long_route.hpp choose_long_route) and the scratch
+// layout of the plan + tiles path (seg_layout, seg_claim_slot) against tables worked out by hand
+// from the rules: host C++ only, exit status 0 when every row agrees.
 #include <cstdint>
 #include <cstdio>
 
@@ -34,6 +35,77 @@ const char* name(LongRoute r) {
     return "?";
 }
 
+// seg_layout: the scratch of one plan + tiles call.  E = sizeof(SegEntry) = 216 words = 864.
+struct LayoutRow {
+    int id;
+    uint32_t count;
+    uint64_t M, S, long_min;
+    uint64_t ecap, tcap, o_cl, o_part, bytes;
+    uint32_t first_rec;  // the call's order names records first_rec .. first_rec + count - 1
+};
+
+int layout_rows() {
+    static_assert(sizeof(enet::SegEntry) == 864, "SegEntry: 8 + 8 + 200 words");
+    const LayoutRow rows[] = {
+        // 512 records named out of 1024 (indices 512 .. 1023): 508 of 40 bytes and 65 553 +
+        // 131 072 + 196 607 + 200 000, S = 20 320 + 593 232 = 613 552.  S / 64 KiB = 9:
+        // ecap = min(512, 9 + 1) = 10, tcap = 9 + 10 + 1 = 20, o_cl = 256 + 10 E = 8 896,
+        // o_part = roundup256(8 896 + 512 = 9 408) = 9 472, bytes = 9 472 + 20 * 32 = 10 112.
+        // (The 11 tiles those four records claim put live partials at [9 472, 9 824): a claim byte
+        // indexed by RECORD would sit at 8 896 + 576 .. 927 inside them, at 8 896 + 1 023 = 9 919
+        // for the last record.)
+        {101, 512, 200000, 613552, 65536, 10, 20, 8896, 9472, 10112, 512},
+        // long_min == 0: every record may be claimed (ecap = n); lengths 0, 1, 100, 65 537, 200 000:
+        // S = 265 638, S / 64 KiB = 4, tcap = 4 + 5 + 1 = 10, o_cl = 256 + 5 E = 4 576,
+        // o_part = roundup256(4 581) = 4 608, bytes = 4 608 + 320
+        {102, 5, 200000, 265638, 0, 5, 10, 4576, 4608, 4928, 0},
+        // the same batch with unknown hints (0 / 0): total = 0, ecap = 5, tcap = 0 + 5 + 1 = 6
+        {103, 5, 0, 0, 0, 5, 6, 4576, 4608, 4800, 0},
+        // unknown hints and a threshold: total = 0, ecap = min(3, 0 + 1) = 1, tcap = 2,
+        // o_cl = 256 + E = 1 120, o_part = roundup256(1 123) = 1 280
+        {104, 3, 0, 0, 65536, 1, 2, 1120, 1280, 1344, 0},
+        // total_bytes_hint == 0 with a known longest record: total = min(n, 1024) * M =
+        // 1024 * 307 200 = 314 572 800; ecap = min(2000, 1200 + 1), tcap = 4800 + 1201 + 1,
+        // o_cl = 256 + 1201 E = 1 037 920, o_part = roundup256(1 039 920) = 1 040 128
+        {105, 2000, 307200, 0, 262144, 1201, 6002, 1037920, 1040128, 1232192, 70000},
+        // the claim bytes end exactly on a 256-byte line (8 896 + 320 = 9 216), and one past it
+        {106, 320, 200000, 613552, 65536, 10, 20, 8896, 9216, 9856, 0xFFFFFEC0u},
+        {107, 321, 200000, 613552, 65536, 10, 20, 8896, 9472, 10112, 1},
+    };
+    int bad = 0;
+    for (const LayoutRow& w : rows) {
+        const enet::SegLayout l = enet::seg_layout(w.count, (uint32_t)w.M, w.S, w.long_min);
+        bool ok = l.ecap == w.ecap && l.tcap == w.tcap && l.o_ent == 256 && l.o_cl == w.o_cl &&
+                  l.o_part == w.o_part && l.bytes == w.bytes;
+        // the invariants behind the figures: entries, then one claim byte per position, then the
+        // partials on a 256-byte line of their own, tcap * 32 bytes of them
+        ok = ok && l.o_cl == l.o_ent + l.ecap * sizeof(enet::SegEntry) && l.o_part % 256 == 0 &&
+             l.o_part >= l.o_cl + w.count && l.o_part < l.o_cl + w.count + 256 &&
+             l.bytes == l.o_part + l.tcap * 32 && l.ecap <= w.count;
+        // every claim byte the kernels touch lies in [o_cl, o_cl + count), short of the partials,
+        // whichever records the order names
+        uint64_t worst = 0;
+        for (uint32_t pos = 0; pos < w.count; ++pos) {
+            const uint64_t at = l.o_cl + enet::seg_claim_slot(pos, w.first_rec + pos);
+            if (at > worst) worst = at;
+        }
+        const bool inside = worst < l.o_cl + w.count && worst < l.o_part;
+        std::printf("layout %d: ecap %llu tcap %llu o_cl %llu o_part %llu bytes %llu, last claim byte %llu%s\n", w.id,
+                    (unsigned long long)l.ecap, (unsigned long long)l.tcap, (unsigned long long)l.o_cl,
+                    (unsigned long long)l.o_part, (unsigned long long)l.bytes, (unsigned long long)worst,
+                    ok && inside ? "" : "   <-- MISMATCH");
+        if (!ok)
+            std::printf("        wanted ecap %llu tcap %llu o_cl %llu o_part %llu bytes %llu\n",
+                        (unsigned long long)w.ecap, (unsigned long long)w.tcap, (unsigned long long)w.o_cl,
+                        (unsigned long long)w.o_part, (unsigned long long)w.bytes);
+        if (!inside)
+            std::printf("        a claim byte lies outside [%llu, %llu)\n", (unsigned long long)l.o_cl,
+                        (unsigned long long)(l.o_cl + w.count));
+        bad += !(ok && inside);
+    }
+    return bad;
+}
+
 }  // namespace
 
 int main() {
@@ -57,13 +129,13 @@ int main() {
         {11, 1000, MODE_SEAL, false, 5, 500, 2500, LongRoute::PlanTiles, 1000},
         // 40000 * 65536 tiles >= 0x7FFFFFFF: the AEAD launch's tile cap
         {12, 0, MODE_SEAL, false, 40000, 4294967295ull, 40000 * 4294967295ull, LongRoute::PlanTiles, kAny},
-        // Known defect, pinned: the uniform routes do not require
-        // max_len_hint != 0, so setting 0 with hints 0 / 0 is a UniformXor launch with L = 0, a
-        // silent no-op.  The XOR route has no tile-count cap either (row 15).
-        {13, 0, MODE_XOR, false, 3, 0, 0, LongRoute::UniformXor, kAny},
+        // hints 0 / 0 mean "unknown", not "uniform of length 0": a one-launch route sized by them
+        // would hold no tile and write nothing.  Planned instead (rows 22, 23: seal and open).
+        {13, 0, MODE_XOR, false, 3, 0, 0, LongRoute::PlanTiles, 0},
         // the frame modes (3, 4) never take the tiles
         {14, -1, 3, false, 4, 300 * KiB, 4 * 300 * KiB, LongRoute::RecordEngine, kAny},
-        {15, 0, MODE_XOR, false, 40000, 4294967295ull, 40000 * 4294967295ull, LongRoute::UniformXor, kAny},
+        // the XOR launch has row 12's tile cap too (its grid would not launch)
+        {15, 0, MODE_XOR, false, 40000, 4294967295ull, 40000 * 4294967295ull, LongRoute::PlanTiles, kAny},
         // beyond the issue's rows: the other side of each threshold
         {16, -1, MODE_OPEN, false, 4, 262144, 4 * 262144ull, LongRoute::UniformAead, 262144},
         {17, -1, MODE_XOR, false, 8192, 262144, 8192 * 262144ull, LongRoute::RecordEngine, kAny},
@@ -71,6 +143,14 @@ int main() {
         {19, 1000, MODE_OPEN, true, 5, 1000, 5000, LongRoute::PlanTiles, 1000},
         {20, INT64_MAX, MODE_XOR, false, 4, 300 * KiB, 4 * 300 * KiB, LongRoute::RecordEngine, (uint64_t)INT64_MAX},
         {21, 0, 4, false, 4, 300 * KiB, 4 * 300 * KiB, LongRoute::RecordEngine, kAny},
+        {22, 0, MODE_SEAL, false, 3, 0, 0, LongRoute::PlanTiles, 0},
+        {23, 0, MODE_OPEN, false, 3, 0, 0, LongRoute::PlanTiles, 0},
+        // unknown hints under the automatic rule never want the tiles; a known length under
+        // setting 0 is still one launch, and the largest tile count under the cap is too
+        {24, -1, MODE_SEAL, false, 3, 0, 0, LongRoute::RecordEngine, kAny},
+        {25, 0, MODE_XOR, false, 3, 1, 3, LongRoute::UniformXor, 0},
+        {26, 0, MODE_XOR, false, 32767, 4294967295ull, 32767 * 4294967295ull, LongRoute::UniformXor, kAny},
+        {27, 0, MODE_XOR, false, 32768, 4294967295ull, 32768 * 4294967295ull, LongRoute::PlanTiles, kAny},
     };
     int bad = 0;
     for (const Row& w : rows) {
@@ -86,5 +166,6 @@ int main() {
             ++bad;
         }
     }
+    bad += layout_rows();
     return bad ? 1 : 0;
 }

@@ -1,6 +1,8 @@
 """The routing rule for long records (csrc/long_route.hpp choose_long_route: record engine,
-one-launch uniform XOR / AEAD, or plan + tiles) against a hand-made table, tests/cpp/route_table.cpp.
-CPU only: the header is plain C++ and is compiled with g++ alone."""
+one-launch uniform XOR / AEAD, or plan + tiles) and the plan + tiles scratch layout (seg_layout: one
+claim byte per position of the launch, partials 256-aligned behind them; seg_claim_slot: the byte a
+record owns, whatever index a caller's order gives it) against hand-made tables,
+tests/cpp/route_table.cpp.  CPU only: the header is plain C++ and is compiled with g++ alone."""
 import os
 import subprocess
 
