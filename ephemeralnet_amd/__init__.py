@@ -76,7 +76,11 @@ EXPORTS = [
     "enet_host_cpu_budget", "enet_host_pinned_bytes", "enet_host_plan", "enet_host_register",
     "enet_host_unregister", "enet_shamir_split_batch", "enet_shamir_combine_batch",
     "enet_handshake_accept_batch", "enet_session_rotate_batch", "enet_key_exchange_batch",
+    "enet_chunk_frame_seal_batch", "enet_chunk_frame_open_batch",
 ]
+
+# status of chunk_frame_open (enet_crypto.h): the first failed check
+ENET_CF_OK, ENET_CF_FRAME, ENET_CF_HEADER, ENET_CF_CHUNK_ID, ENET_CF_HASH = 0, 1, 2, 3, 4
 
 # verdicts of handshake_accept (enet_crypto.h)
 ENET_HS_BAD_PUBLIC, ENET_HS_OK, ENET_HS_BAD_POW, ENET_HS_BAD_SLOT = 0, 1, 2, 3
@@ -229,6 +233,8 @@ def lib() -> C.CDLL:
         L.enet_handshake_accept_batch.argtypes = [tp, u32, vp, vp, vp, vp, vp, u32, u32, u32, C.c_int64, vp, vp]
         L.enet_session_rotate_batch.argtypes = [tp, C.c_int64, C.c_int64, vp, vp]
         L.enet_key_exchange_batch.argtypes = [u32, vp, vp, vp, vp, vp]
+        L.enet_chunk_frame_seal_batch.argtypes = [rp, vp, u32, vp, vp, vp, vp, vp]
+        L.enet_chunk_frame_open_batch.argtypes = [rp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         for name in EXPORTS:
             getattr(L, name)
         _lib = L
@@ -442,6 +448,35 @@ def chunk_fetch(b: Batch, out, chunk_ids, chunk_hashes, ok, stream=None) -> None
     r = b.records(out, b.offsets)
     _check(lib().enet_chunk_fetch_batch(C.byref(r), _ptr(chunk_ids), _ptr(chunk_hashes), _ptr(ok),
                                         _stream(stream)), "enet_chunk_fetch_batch")
+
+
+def chunk_frame_seal(b: Batch, out, out_offsets, chunk_ids, ttl, versions=None, session=None, sessions=0,
+                     mid=None, stream=None) -> None:
+    """Upload (Node::dispatch_upload): b.arena holds the stored chunk ciphertexts, b.nonces the frame
+    nonces, b.keys the session keys (per record, or the table when `session` int32 [n] / `sessions` /
+    `mid` are given); out_i = the wire frame of the Chunk message version || 0x03 || BE32(ttl_i) ||
+    BE32(|data_i|) || chunk_ids[i] || data_i, |out_i| = |data_i| + 90.  chunk_ids uint8 [n,32], ttl
+    int32 [n] seconds, versions uint8 [n] (None = 4; clamped to 1..4)."""
+    r = b.records(out, out_offsets)
+    _check(lib().enet_chunk_frame_seal_batch(C.byref(r), _ptr(session), sessions, _ptr(mid), _ptr(chunk_ids),
+                                             _ptr(ttl), _ptr(versions), _stream(stream)),
+           "enet_chunk_frame_seal_batch")
+
+
+def chunk_frame_open(b: Batch, out, out_offsets, chunk_ids, chunk_keys, chunk_nonces, chunk_hashes, status,
+                     data_out=None, ttl_out=None, session=None, sessions=0, mid=None, stream=None) -> None:
+    """Receive (receive_loop -> decode_signed -> decode -> receive_chunk): b.arena holds received wire
+    frames (nonces come from the frames; b.nonces may be None), b.keys the session keys as in
+    chunk_frame_seal; chunk_ids / chunk_keys / chunk_nonces / chunk_hashes uint8 [n,32|32|12|32] are
+    what the manifest expects (chunk_keys may be shamir_combine's output on the same stream).
+    out_i = the plaintext (|in_i| - 90 bytes), data_out (same offsets) the chunk ciphertext to store,
+    ttl_out int32 [n], status uint8 [n] = ENET_CF_*: the first failed check; a failed record's
+    plaintext, data_out and ttl_out are zero."""
+    r = b.records(out, out_offsets)
+    _check(lib().enet_chunk_frame_open_batch(C.byref(r), _ptr(session), sessions, _ptr(mid), _ptr(chunk_ids),
+                                             _ptr(chunk_keys), _ptr(chunk_nonces), _ptr(chunk_hashes),
+                                             _ptr(data_out), _ptr(ttl_out), _ptr(status), _stream(stream)),
+           "enet_chunk_frame_open_batch")
 
 
 def pow_search(prefixes, offsets, difficulty, schedule: int, max_attempts: int, nonces, found,

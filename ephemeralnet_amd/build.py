@@ -24,6 +24,7 @@ OBJ = os.path.join(PKG, "build")
 LIB_TOOLS = os.path.join(PKG, "libenet_crypto_tools.so")
 OBJ_TOOLS = os.path.join(PKG, "build_tools")
 SOURCES = ["records.hip", "segments.hip", "stream.hip", "sha.hip", "pow.hip", "duplex.hip", "duplex_split.hip",
+           "chunk_frames.hip",
            "shamir.hip", "shamir_host.cpp", "handshake.hip",
            "capi.cpp", "long_records.cpp", "chunk_hybrid.cpp", "crypto_api.cpp", "pipeline.cpp", "host_engine.cpp",
            "frame_queue.cpp", "host_batch.cpp", "host_topo.cpp"]

@@ -834,6 +834,57 @@ int enet_wire_open_batch(const enet_records* r, uint8_t* macs, uint8_t* ok, void
     return frame_open(&q, kWireHeader, macs, ok, (hipStream_t)stream, "wire_open");
 }
 
+// chunk transfer frames: the session keys per record (session == NULL) or as a table
+static int chunk_frame_keys(enet::ChunkFrameParams& c, const uint32_t* session, uint32_t sessions,
+                            const uint32_t* mid, const char* what) {
+    if (!session) return ENET_OK;
+    if (!mid || !aligned4(session) || !aligned4(mid) || sessions == 0) return fail(ENET_EINVAL, what);
+    c.d.session = session;
+    c.d.mid = mid;
+    c.d.n_sessions = sessions;
+    return ENET_OK;
+}
+
+int enet_chunk_frame_seal_batch(const enet_records* r, const uint32_t* session, uint32_t sessions,
+                                const uint32_t* mid, const uint8_t* chunk_ids, const uint32_t* ttl,
+                                const uint8_t* versions, void* stream) {
+    if (int e = check_records(r, true)) return e;
+    if (r->count == 0) return ENET_OK;
+    if (!chunk_ids || !ttl || !aligned4(ttl)) return fail(ENET_EINVAL, "chunk_frame_seal: NULL chunk_ids, NULL/misaligned ttl");
+    enet::ChunkFrameParams c{};
+    c.d = duplex_params(r);
+    if (int e = chunk_frame_keys(c, session, sessions, mid, "chunk_frame_seal: NULL/misaligned session or mid, or no sessions")) return e;
+    c.chunk_ids = chunk_ids;
+    c.ttl = ttl;
+    c.versions = versions;
+    return hip_status(enet::launch_chunk_frames(false, c, (hipStream_t)stream), "chunk_frame_seal");
+}
+
+int enet_chunk_frame_open_batch(const enet_records* r, const uint32_t* session, uint32_t sessions,
+                                const uint32_t* mid, const uint8_t* chunk_ids, const uint8_t* chunk_keys,
+                                const uint8_t* chunk_nonces, const uint8_t* chunk_hashes, uint8_t* data_out,
+                                uint32_t* ttl_out, uint8_t* status, void* stream) {
+    if (!r) return fail(ENET_EINVAL, "records descriptor is NULL");
+    if (!status) return fail(ENET_EINVAL, "chunk_frame_open: NULL status");
+    if (!chunk_ids || !chunk_keys || !chunk_nonces || !chunk_hashes)
+        return fail(ENET_EINVAL, "chunk_frame_open: NULL chunk_ids, chunk_keys, chunk_nonces or chunk_hashes");
+    if (ttl_out && !aligned4(ttl_out)) return fail(ENET_EINVAL, "chunk_frame_open: ttl_out misaligned");
+    if (r->count == 0) return ENET_OK;
+    const enet_records q = with_frame_nonce(r);
+    if (int e = check_records(&q, true)) return e;
+    enet::ChunkFrameParams c{};
+    c.d = duplex_params(&q);
+    if (int e = chunk_frame_keys(c, session, sessions, mid, "chunk_frame_open: NULL/misaligned session or mid, or no sessions")) return e;
+    c.chunk_ids = chunk_ids;
+    c.chunk_keys = chunk_keys;
+    c.chunk_nonces = chunk_nonces;
+    c.chunk_hashes = chunk_hashes;
+    c.data_out = data_out;
+    c.ttl_out = ttl_out;
+    c.status = status;
+    return hip_status(enet::launch_chunk_frames(true, c, (hipStream_t)stream), "chunk_frame_open");
+}
+
 int enet_pow_search_batch(uint32_t n, const uint8_t* prefixes, const uint64_t* prefix_offsets,
                           const uint8_t* difficulty, int schedule, uint64_t max_attempts,
                           uint64_t* nonces, uint64_t* attempts, uint8_t* found, void* stream) {

@@ -1336,6 +1336,127 @@ std::vector<std::vector<std::uint8_t>> wire_open_sessions(std::span<const std::a
     return res;
 }
 
+// ---- chunk transfer frames (enet_chunk_frame_*_batch): every per-record array travels in one
+// buffer, each part at a 4-byte aligned offset
+std::vector<std::vector<std::uint8_t>> chunk_frames_seal(std::span<const std::array<std::uint8_t, 32>> session_table,
+                                                         std::span<const std::uint32_t> session,
+                                                         std::span<const Nonce> nonces, std::span<const ChunkId> chunk_ids,
+                                                         std::span<const std::uint32_t> ttl_seconds,
+                                                         std::span<const std::span<const std::uint8_t>> stored,
+                                                         std::span<const std::uint8_t> versions) {
+    const std::size_t n = stored.size(), K = session_table.size();
+    if (session.size() != n || nonces.size() != n || chunk_ids.size() != n || ttl_seconds.size() != n ||
+        (!versions.empty() && versions.size() != n))
+        throw std::invalid_argument("enet batch::chunk_frames_seal: size mismatch");
+    check_count(n, "chunk_frames_seal");
+    if (n == 0) return {};
+    check_sessions(session, K, "chunk_frames_seal");
+    const Packed in = pack(stored);
+    const std::vector<std::uint64_t> ooff = offsets_of(stored, 90);
+    // keys | chunk ids | ttl | nonces | versions
+    const std::size_t o_id = 32 * n, o_ttl = 64 * n, o_non = 68 * n, o_ver = 80 * n;
+    std::vector<std::uint8_t> meta(81 * n);
+    for (std::size_t i = 0; i < n; ++i) std::memcpy(meta.data() + 32 * i, session_table[session[i]].data(), 32);
+    std::memcpy(meta.data() + o_id, chunk_ids.data()->data(), 32 * n);
+    std::memcpy(meta.data() + o_ttl, ttl_seconds.data(), 4 * n);
+    std::memcpy(meta.data() + o_non, nonce_bytes(nonces), 12 * n);
+    if (!versions.empty()) std::memcpy(meta.data() + o_ver, versions.data(), n);
+    return staged([&](Staging& st) {
+        const std::size_t obytes = ooff[n];
+        auto* din = (uint8_t*)st.get(S_IN, in.arena.size());
+        auto* dout = (uint8_t*)st.get(S_OUT, obytes);
+        auto* dioff = (uint64_t*)st.get(S_INOFF, 8 * (n + 1));
+        auto* dooff = (uint64_t*)st.get(S_OUTOFF, 8 * (n + 1));
+        auto* dm = (uint8_t*)st.get(S_KEYS, meta.size());
+        st.h2d(din, in.arena.data(), in.arena.size());
+        st.h2d(dioff, in.off.data(), 8 * (n + 1));
+        st.h2d(dooff, ooff.data(), 8 * (n + 1));
+        st.h2d(dm, meta.data(), meta.size());
+        enet_records r{};
+        r.count = (uint32_t)n;
+        r.in_offsets = dioff;
+        r.out_offsets = dooff;
+        r.in = din;
+        r.out = dout;
+        r.keys = dm;
+        r.key_stride = 32;
+        r.nonces = dm + o_non;
+        enet_check(enet_chunk_frame_seal_batch(&r, nullptr, 0, nullptr, dm + o_id, reinterpret_cast<const uint32_t*>(dm + o_ttl),
+                                               versions.empty() ? nullptr : dm + o_ver, st.s()),
+                   "chunk_frame_seal");
+        std::vector<std::uint8_t> flat(obytes);
+        st.d2h(flat.data(), dout, obytes);
+        st.sync();
+        std::vector<std::vector<std::uint8_t>> res(n);
+        for (std::size_t i = 0; i < n; ++i) res[i].assign(flat.begin() + ooff[i], flat.begin() + ooff[i + 1]);
+        return res;
+    });
+}
+
+std::vector<OpenedChunk> chunk_frames_open(std::span<const std::array<std::uint8_t, 32>> session_table,
+                                           std::span<const std::uint32_t> session,
+                                           std::span<const std::span<const std::uint8_t>> frames,
+                                           std::span<const ChunkId> chunk_ids, std::span<const Key> chunk_keys,
+                                           std::span<const Nonce> chunk_nonces,
+                                           std::span<const std::array<std::uint8_t, 32>> chunk_hashes) {
+    const std::size_t n = frames.size(), K = session_table.size();
+    if (session.size() != n || chunk_ids.size() != n || chunk_keys.size() != n || chunk_nonces.size() != n ||
+        chunk_hashes.size() != n)
+        throw std::invalid_argument("enet batch::chunk_frames_open: size mismatch");
+    check_count(n, "chunk_frames_open");
+    if (n == 0) return {};
+    check_sessions(session, K, "chunk_frames_open");
+    const Packed in = pack(frames);
+    const std::vector<std::uint64_t> ooff = offsets_of(frames, -90);
+    // session keys | chunk ids | chunk keys | chunk hashes | chunk nonces
+    const std::size_t o_id = 32 * n, o_ck = 64 * n, o_h = 96 * n, o_cn = 128 * n;
+    std::vector<std::uint8_t> meta(140 * n);
+    for (std::size_t i = 0; i < n; ++i) std::memcpy(meta.data() + 32 * i, session_table[session[i]].data(), 32);
+    std::memcpy(meta.data() + o_id, chunk_ids.data()->data(), 32 * n);
+    std::memcpy(meta.data() + o_ck, key_bytes(chunk_keys), 32 * n);
+    std::memcpy(meta.data() + o_h, chunk_hashes.data()->data(), 32 * n);
+    std::memcpy(meta.data() + o_cn, nonce_bytes(chunk_nonces), 12 * n);
+    return staged([&](Staging& st) {
+        const std::size_t obytes = ooff[n];
+        auto* din = (uint8_t*)st.get(S_IN, in.arena.size());
+        auto* dpt = (uint8_t*)st.get(S_OUT, obytes);
+        auto* dct = (uint8_t*)st.get(S_AUX, obytes);
+        auto* dioff = (uint64_t*)st.get(S_INOFF, 8 * (n + 1));
+        auto* dooff = (uint64_t*)st.get(S_OUTOFF, 8 * (n + 1));
+        auto* dm = (uint8_t*)st.get(S_KEYS, meta.size());
+        auto* dres = (uint8_t*)st.get(S_OK, 5 * n);  // ttl [n] uint32, then status [n]
+        st.h2d(din, in.arena.data(), in.arena.size());
+        st.h2d(dioff, in.off.data(), 8 * (n + 1));
+        st.h2d(dooff, ooff.data(), 8 * (n + 1));
+        st.h2d(dm, meta.data(), meta.size());
+        enet_records r{};
+        r.count = (uint32_t)n;
+        r.in_offsets = dioff;
+        r.out_offsets = dooff;
+        r.in = din;
+        r.out = dpt;
+        r.keys = dm;
+        r.key_stride = 32;
+        enet_check(enet_chunk_frame_open_batch(&r, nullptr, 0, nullptr, dm + o_id, dm + o_ck, dm + o_cn, dm + o_h, dct,
+                                               reinterpret_cast<uint32_t*>(dres), dres + 4 * n, st.s()),
+                   "chunk_frame_open");
+        std::vector<std::uint8_t> pt(obytes), ct(obytes), resv(5 * n);
+        st.d2h(pt.data(), dpt, obytes);
+        st.d2h(ct.data(), dct, obytes);
+        st.d2h(resv.data(), dres, resv.size());
+        st.sync();
+        std::vector<OpenedChunk> res(n);
+        for (std::size_t i = 0; i < n; ++i) {
+            res[i].status = static_cast<ChunkFrameStatus>(resv[4 * n + i]);
+            if (res[i].status != ChunkFrameStatus::Ok) continue;  // no plaintext, ciphertext or ttl of a failed frame
+            std::memcpy(&res[i].ttl_seconds, resv.data() + 4 * i, 4);
+            res[i].plaintext.assign(pt.begin() + ooff[i], pt.begin() + ooff[i + 1]);
+            res[i].stored.assign(ct.begin() + ooff[i], ct.begin() + ooff[i + 1]);
+        }
+        return res;
+    });
+}
+
 // ------------------------------------------------------------------------------ proof of work
 namespace {
 void put_be64(std::vector<std::uint8_t>& v, std::uint64_t x) {

@@ -134,6 +134,25 @@ hipError_t launch_duplex_split(int kind, bool open, const DuplexParams& p, hipSt
 // -1 auto (split when the longest record is >= 16 KiB), 0 never, 1 always (chunk / AEADH kinds)
 int duplex_split_mode();
 
+// Chunk transfer frames (chunk_frames.hip): a `Chunk` message (Message.cpp:204-246) inside a wire
+// frame, sealed from / opened to the stored chunk in one pass.  d carries the arenas, offsets,
+// order, the session keys (per record, or the table with session / mid / n_sessions) and, for
+// seal, the frame nonces; the rest are [n] device arrays at any alignment unless noted.
+constexpr uint32_t kChunkFrameHeader = 42;  // version, type, BE32 ttl, BE32 |data|, chunk_id(32)
+struct ChunkFrameParams {
+    DuplexParams d;
+    const uint8_t* chunk_ids;     // [n][32]: seal puts it in the header, open expects it there
+    const uint32_t* ttl;          // seal: seconds (4-byte aligned)
+    const uint8_t* versions;      // seal, nullable: clamped to 1..4; NULL = 4
+    const uint8_t* chunk_keys;    // open [n][32]
+    const uint8_t* chunk_nonces;  // open [n][12]
+    const uint8_t* chunk_hashes;  // open [n][32]: SHA-256(plaintext) the manifest promises
+    uint8_t* data_out;            // open, nullable: the chunk ciphertext, at out_off
+    uint32_t* ttl_out;            // open, nullable (4-byte aligned)
+    uint8_t* status;              // open: 0 ok, 1 FRAME, 2 HEADER, 3 CHUNK_ID, 4 HASH
+};
+hipError_t launch_chunk_frames(bool open, const ChunkFrameParams& p, hipStream_t s);
+
 // Proof-of-work search / check (pow.hip): SHA-256(prefix_i || BE64(candidate)).
 struct PowParams {
     uint32_t n;

@@ -183,6 +183,65 @@ ENET_API int enet_chunk_store_batch(const enet_records* r, const uint8_t* chunk_
 ENET_API int enet_chunk_fetch_batch(const enet_records* r, const uint8_t* chunk_ids,
                                     const uint8_t* chunk_hashes, uint8_t* ok, void* stream);
 
+/* ---- Chunk transfer frames: a stored chunk onto the wire and off it in one pass each
+ *      (additive to ABI 1.4: enet_abi_version() is unchanged, no existing call changes).
+ * Upload (Node::dispatch_upload, src/core/Node.cpp:1254-1297) wraps the stored ciphertext in a
+ * `Chunk` message (encode, src/protocol/Message.cpp:204-246; every version 1..4 writes the same
+ * 42-byte header), signs it (encode_signed, Message.cpp:305-311) and sends it as a session frame
+ * (SessionManager::send, src/network/SessionManager.cpp:362-387):
+ *   m_i     = version || 0x03 || BE32(ttl_i) || BE32(|data_i|) || chunk_id_i(32) || data_i
+ *   frame_i = nonce_i(12) || BE32(|m_i| + 32) || ChaCha20_{Ks_i, nonce_i, 0}(m_i || HMAC_{Ks_i}(m_i))
+ *   data_i  = ChaCha20_{Kc_i, Nc_i, LE32(chunk_id_i[0..3])}(plaintext_i)   (enet_chunk_store_batch)
+ * The receiver (receive_loop, SessionManager.cpp:760-822; decode_signed, Message.cpp:313-328;
+ * decode, Message.cpp:144-159; Node::handle_chunk -> receive_chunk, Node.cpp:2286-2299,
+ * 1615-1677) decrypts the frame, checks the HMAC, parses the header, decrypts data under the
+ * chunk key, compares SHA-256(plaintext) with manifest.chunk_hash, stores the ciphertext
+ * (chunk_store_.put, Node.cpp:1665) and returns the plaintext.
+ * Session keys for both calls: session != NULL -- r->keys is the [sessions][32] table, session[i]
+ * the frame's session and mid the table's enet_hmac_midstates, as in enet_wire_*_batch_sessions;
+ * session == NULL -- r->keys / r->key_stride give each record's key as in enet_wire_seal_batch
+ * (sessions and mid are ignored).  order, total_bytes_hint and max_len_hint keep their
+ * enet_records meaning (hints cost speed, never bytes).  All array arguments are device pointers
+ * ([n] entries, indexed by record): chunk_keys may be the output of enet_shamir_combine_batch.
+ * seal: in_i = data_i, read in place at any alignment; out_i = frame_i, out_offsets must give
+ *       |out_i| = |data_i| + 90 (16 + 42 + 32); r->nonces = the frame nonces; chunk_ids [n][32];
+ *       ttl [n] uint32 seconds; versions [n] uint8, NULL = 4, clamped to 1..4 (clamp_version,
+ *       Message.cpp:17-25).  Same bytes as enet_wire_seal_batch[_sessions] over m_i.  A record
+ *       whose output length does not fit or whose session index is outside the table has its
+ *       whole output slot zeroed.
+ * open: in_i = a received frame (the nonce is read from it; r->nonces is ignored, may be NULL);
+ *       chunk_ids / chunk_keys / chunk_nonces / chunk_hashes [n][32|32|12|32] = what the caller's
+ *       manifest expects; out_i = plaintext_i, out_offsets must give |in_i| - 90 (0 for a frame
+ *       shorter than 90 bytes); data_out (nullable; same out_offsets) = data_i; ttl_out [n]
+ *       uint32 (nullable); status [n] uint8 = the first check that failed:
+ *         0 ENET_CF_OK
+ *         1 ENET_CF_FRAME     frame shorter than 48 bytes, length field != body length, HMAC
+ *                             mismatch, session index outside the table, or the output length
+ *                             does not fit (what gives enet_wire_open_batch ok = 0)
+ *         2 ENET_CF_HEADER    |m| < 42, version outside 1..4, type != 0x03, or BE32 data length
+ *                             != |m| - 42
+ *         3 ENET_CF_CHUNK_ID  the message's chunk id != chunk_ids[i]
+ *         4 ENET_CF_HASH      SHA-256(plaintext_i) != chunk_hashes[i]
+ *       On any non-zero status the record's plaintext range, its data_out range and ttl_out[i]
+ *       are zero when the call returns.  Records `order` does not name are untouched.
+ *       One deliberate difference: decode accepts a Chunk message with bytes after data (its only
+ *       length check is remaining < expected, Message.cpp:151); this call reports
+ *       ENET_CF_HEADER for such a frame (encode never produces one) and the caller falls back to
+ *       enet_wire_open_batch_sessions.
+ * One launch each; open reads every frame byte from HBM once and runs both ciphers and both
+ * hashes of a record concurrently (three lanes per record).  Frames are at most 1 MiB
+ * (SessionManager.cpp:87).  NULL r, status, chunk_ids, chunk_keys, chunk_nonces or chunk_hashes:
+ * ENET_EINVAL. */
+enum { ENET_CF_OK = 0, ENET_CF_FRAME = 1, ENET_CF_HEADER = 2, ENET_CF_CHUNK_ID = 3, ENET_CF_HASH = 4 };
+ENET_API int enet_chunk_frame_seal_batch(const enet_records* r, const uint32_t* session, uint32_t sessions,
+                                         const uint32_t* mid, const uint8_t* chunk_ids, const uint32_t* ttl,
+                                         const uint8_t* versions, void* stream);
+ENET_API int enet_chunk_frame_open_batch(const enet_records* r, const uint32_t* session, uint32_t sessions,
+                                         const uint32_t* mid, const uint8_t* chunk_ids,
+                                         const uint8_t* chunk_keys, const uint8_t* chunk_nonces,
+                                         const uint8_t* chunk_hashes, uint8_t* data_out, uint32_t* ttl_out,
+                                         uint8_t* status, void* stream);
+
 /* ---- proof of work
  * Every PoW in the reference hashes SHA-256(prefix || BE64(candidate)) and accepts the FIRST
  * candidate, in attempt order, whose digest has >= difficulty leading zero bits:

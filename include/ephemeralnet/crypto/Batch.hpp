@@ -180,6 +180,35 @@ ENET_CXX_API std::vector<std::vector<std::uint8_t>> wire_open_sessions(
     std::span<const std::array<std::uint8_t, 32>> session_table, std::span<const std::uint32_t> session,
     std::span<const std::span<const std::uint8_t>> frames, std::vector<std::uint8_t>& ok);
 
+// Chunk transfer frames (enet_chunk_frame_*_batch): a stored chunk onto the wire and off it in one
+// device pass each.  chunk_frames_seal is Node::dispatch_upload's crypto (Node.cpp:1254-1297):
+// frame i = the wire frame, under session_table[session[i]] and nonces[i], of the signed Chunk
+// message version || 0x03 || BE32(ttl_seconds[i]) || BE32(|stored[i]|) || chunk_ids[i] || stored[i]
+// (Message.cpp:204-246, 305-311; SessionManager.cpp:362-387); versions empty = 4, else clamped
+// to 1..4.  chunk_frames_open is the receive side (SessionManager.cpp:760-822, Message.cpp:313-328,
+// 144-159, Node::receive_chunk, Node.cpp:1615-1677): the frame is opened, its header checked
+// against chunk_ids[i], the data decrypted under chunk_keys[i] / chunk_nonces[i] and
+// SHA-256(plaintext) compared with chunk_hashes[i].  status = the first check that failed; a
+// failed frame comes back with empty plaintext and stored and ttl 0.  A Chunk message with bytes
+// after its data reports Header (decode would accept it; encode never writes one).  Throws
+// std::invalid_argument for a size mismatch or a session index outside the table.
+enum class ChunkFrameStatus : std::uint8_t { Ok = 0, Frame = 1, Header = 2, ChunkId = 3, Hash = 4 };
+struct OpenedChunk {
+    ChunkFrameStatus status = ChunkFrameStatus::Frame;
+    std::uint32_t ttl_seconds = 0;
+    std::vector<std::uint8_t> plaintext;  // what receive_chunk returns
+    std::vector<std::uint8_t> stored;     // the chunk ciphertext the node keeps (chunk_store_.put, Node.cpp:1665)
+};
+ENET_CXX_API std::vector<std::vector<std::uint8_t>> chunk_frames_seal(
+    std::span<const std::array<std::uint8_t, 32>> session_table, std::span<const std::uint32_t> session,
+    std::span<const Nonce> nonces, std::span<const ChunkId> chunk_ids, std::span<const std::uint32_t> ttl_seconds,
+    std::span<const std::span<const std::uint8_t>> stored, std::span<const std::uint8_t> versions = {});
+ENET_CXX_API std::vector<OpenedChunk> chunk_frames_open(
+    std::span<const std::array<std::uint8_t, 32>> session_table, std::span<const std::uint32_t> session,
+    std::span<const std::span<const std::uint8_t>> frames, std::span<const ChunkId> chunk_ids,
+    std::span<const Key> chunk_keys, std::span<const Nonce> chunk_nonces,
+    std::span<const std::array<std::uint8_t, 32>> chunk_hashes);
+
 // Cross-session frame queues.  SessionManager runs one detached reader
 // thread per session (SessionManager.cpp:332-333, receive_loop :703-854) and sends from whatever
 // thread calls Node::send_secure (:337-388), one ChaCha20 + HMAC per frame on that thread.  Here
