@@ -26,10 +26,11 @@ OBJ_TOOLS = os.path.join(PKG, "build_tools")
 SOURCES = ["records.hip", "segments.hip", "stream.hip", "sha.hip", "pow.hip", "duplex.hip", "duplex_split.hip",
            "chunk_frames.hip",
            "shamir.hip", "shamir_host.cpp", "handshake.hip",
-           "capi.cpp", "long_records.cpp", "chunk_hybrid.cpp", "crypto_api.cpp", "pipeline.cpp", "host_engine.cpp",
+           "capi.cpp", "long_records.cpp", "chunk_hybrid.cpp", "staging.cpp", "scalar_api.cpp", "batch_records.cpp",
+           "batch_staged.cpp", "pipeline.cpp", "host_engine.cpp",
            "frame_queue.cpp", "host_batch.cpp", "host_topo.cpp"]
 HEADERS = ["enet_device.hpp", "enet_internal.hpp", "long_route.hpp", "record_route.hpp", "long_records.hpp", "records_body.hpp",
-           "stream_common.hpp", "duplex_common.hpp", "host_engine.hpp", "scalar.hpp", "host_batch.hpp", "host_topo.hpp", "gf256.hpp"]
+           "stream_common.hpp", "duplex_common.hpp", "host_engine.hpp", "scalar.hpp", "staging.hpp", "api_common.hpp", "host_batch.hpp", "host_topo.hpp", "gf256.hpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC",
           "-fvisibility=hidden", "-Wall", "-Wno-unused-function",

@@ -30,6 +30,7 @@
 #include "enet_crypto.h"
 #include "enet_internal.hpp"
 #include "host_topo.hpp"
+#include "staging.hpp"
 
 #include <pthread.h>
 
@@ -37,14 +38,8 @@ namespace enet::hb {
 
 namespace {
 
-void hip_check(hipError_t e, const char* what) {
-    if (e != hipSuccess) throw std::runtime_error(std::string("enet host batch: ") + what + ": " + hipGetErrorString(e));
-}
-
-void enet_check(int rc, const char* what) {
-    if (rc != ENET_OK)
-        throw std::runtime_error(std::string("enet host batch: ") + what + ": " + enet_last_error());
-}
+using stage::enet_check;
+using stage::hip_check;
 
 // ------------------------------------------------------------------------------ worker pool
 // parallel(parts, fn): fn(0..parts-1) on the pool's threads and the caller, returns when all ran.

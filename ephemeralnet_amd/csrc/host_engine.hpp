@@ -5,7 +5,7 @@
 // session threads (SessionManager.cpp:332,703), and a GPU round trip costs >= ~18 us before any
 // byte moves.  SHA-256 of one message is a serial Merkle-Damgard chain (one GPU lane runs it
 // ~16x slower than a core), and a 98-byte HMAC or a 1500-byte frame is done on a core in about a
-// microsecond.  So the scalar C++ drop-in (crypto_api.cpp) runs serial and small work here and
+// microsecond.  So the scalar C++ drop-in (scalar_api.cpp) runs serial and small work here and
 // sends only large ChaCha20 calls -- coalesced across threads -- and every batch entry point to
 // the MI355X.  This is a first-class path chosen by size, not a fallback of the GPU kernels: the
 // C ABI's batch entry points never come here.  It is the builder's own code (RFC 8439 / FIPS

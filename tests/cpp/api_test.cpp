@@ -36,6 +36,195 @@ static std::string hex(const T& v) {
     return s.empty() ? "-" : s;
 }
 
+// what() of the std::invalid_argument `f` throws; "no-throw" / "other: ..." otherwise
+template <class F>
+static std::string thrown(F&& f) {
+    try {
+        f();
+    } catch (const std::invalid_argument& e) {
+        return e.what();
+    } catch (const std::exception& e) {
+        return std::string("other: ") + e.what();
+    }
+    return "no-throw";
+}
+
+// Argument handling of every crypto::batch / security::batch entry point, none of it reaching the
+// device: size mismatches, contiguous outputs one byte short, empty batches.  One line per case:
+// "<kind> <label> | <result>".
+static void batch_args() {
+    namespace B = crypto::batch;
+    using Bytes = std::vector<uint8_t>;
+    using K32 = std::array<uint8_t, 32>;
+    const Bytes r0(1, 0xA1), r1(65, 0xB2);
+    const std::span<const uint8_t> recs[2] = {r0, r1};
+    const std::span<const std::span<const uint8_t>> in2(recs), in0;
+    const crypto::Key keys[2]{};
+    const crypto::Nonce nonces[2]{};
+    const K32 k32[2]{};
+    const ChunkId ids[2]{};
+    const std::array<uint8_t, 16> tags[2]{};
+    std::array<uint8_t, 16> tags_out[2]{};
+    const uint32_t u32[2] = {0, 1};
+    const uint64_t u64[2] = {0, 1};
+    const int64_t i64[2] = {0, 1};
+    const uint8_t u8[2] = {1, 1};
+    uint8_t ok2[2] = {};
+    const std::vector<crypto::ShamirShare> shares[2] = {std::vector<crypto::ShamirShare>(2),
+                                                        std::vector<crypto::ShamirShare>(2)};
+    const security::StoreWorkInput work[2]{};
+    Bytes big(512);
+    std::vector<Bytes> vv;
+    std::vector<B::Sealed> sv;
+    Bytes ok;
+    // std::span(ptr, 1): every per-record array one entry short of the two records
+    auto one = [](auto* p) { return std::span(p, 1); };
+    auto two = [](auto* p) { return std::span(p, 2); };
+
+    auto mismatch = [](const char* label, auto&& f) { std::cout << "mismatch " << label << " | " << thrown(f) << "\n"; };
+    mismatch("chacha20_apply/ret", [&] { (void)B::chacha20_apply(one(keys), two(nonces), in2, {}); });
+    mismatch("chacha20_apply/ret-counters", [&] { (void)B::chacha20_apply(two(keys), two(nonces), in2, one(u32)); });
+    mismatch("chacha20_apply/vec", [&] { B::chacha20_apply(two(keys), one(nonces), in2, {}, vv); });
+    mismatch("chacha20_apply/span", [&] { B::chacha20_apply(one(keys), two(nonces), in2, {}, std::span<uint8_t>(big)); });
+    mismatch("aead_seal/ret", [&] { (void)B::aead_seal(one(keys), two(nonces), in2); });
+    mismatch("aead_seal/vec", [&] { B::aead_seal(two(keys), one(nonces), in2, sv); });
+    mismatch("aead_seal/span", [&] { B::aead_seal(two(keys), two(nonces), in2, std::span<uint8_t>(big), one(tags_out)); });
+    mismatch("aead_open/ret", [&] { (void)B::aead_open(two(keys), two(nonces), in2, one(tags), ok); });
+    mismatch("aead_open/vec", [&] { B::aead_open(one(keys), two(nonces), in2, two(tags), vv, ok); });
+    mismatch("aead_open/span", [&] {
+        B::aead_open(two(keys), two(nonces), in2, two(tags), std::span<uint8_t>(big), std::span<uint8_t>(ok2, 1));
+    });
+    mismatch("frame_seal", [&] { (void)B::frame_seal(one(k32), two(nonces), in2); });
+    mismatch("frame_open", [&] { (void)B::frame_open(two(k32), one(nonces), in2, ok); });
+    mismatch("chunk_store", [&] { (void)B::chunk_store(two(keys), two(nonces), in2, one(ids)); });
+    mismatch("chunk_fetch", [&] { (void)B::chunk_fetch(two(keys), two(nonces), two(ids), in2, one(k32), ok); });
+    mismatch("chunk_store_shared", [&] { (void)B::chunk_store_shared(one(nonces), in2, {}, 2, 3); });
+    mismatch("chunk_fetch_shared", [&] {
+        (void)B::chunk_fetch_shared(one(shares), 2, two(nonces), two(ids), in2, two(k32), ok);
+    });
+    mismatch("wire_seal/ret", [&] { (void)B::wire_seal(one(k32), two(nonces), in2); });
+    mismatch("wire_seal/vec", [&] { B::wire_seal(two(k32), one(nonces), in2, vv); });
+    mismatch("wire_seal/span", [&] { B::wire_seal(one(k32), two(nonces), in2, std::span<uint8_t>(big)); });
+    mismatch("wire_open/ret", [&] { (void)B::wire_open(one(k32), in2, ok); });
+    mismatch("wire_open/vec", [&] { B::wire_open(one(k32), in2, vv, ok); });
+    mismatch("wire_open/span", [&] { B::wire_open(two(k32), in2, std::span<uint8_t>(big), std::span<uint8_t>(ok2, 1)); });
+    mismatch("wire_seal_sessions", [&] { (void)B::wire_seal_sessions(two(k32), one(u32), two(nonces), in2); });
+    mismatch("wire_open_sessions", [&] { (void)B::wire_open_sessions(two(k32), one(u32), in2, ok); });
+    mismatch("chunk_frames_seal", [&] {
+        (void)B::chunk_frames_seal(two(k32), two(u32), two(nonces), two(ids), one(u32), in2);
+    });
+    mismatch("chunk_frames_seal/versions", [&] {
+        (void)B::chunk_frames_seal(two(k32), two(u32), two(nonces), two(ids), two(u32), in2, one(u8));
+    });
+    mismatch("chunk_frames_open", [&] {
+        (void)B::chunk_frames_open(two(k32), two(u32), in2, two(ids), two(keys), one(nonces), two(k32));
+    });
+    mismatch("pow_search", [&] { (void)B::pow_search(in2, one(u8), B::PowSchedule::Node, 10); });
+    mismatch("pow_check", [&] { (void)B::pow_check(in2, one(u64), two(u8)); });
+    mismatch("session_keys", [&] { (void)B::session_keys(two(keys), two(u64), one(i64)); });
+    mismatch("key_exchange", [&] { (void)B::key_exchange(two(u32), one(u32)); });
+    mismatch("store_pow_valid", [&] { (void)security::batch::store_pow_valid(two(work), one(u64), 4); });
+
+    // contiguous outputs one byte short: records of 1 and 65 bytes
+    auto small = [&](const char* label, size_t need, auto&& f) {
+        Bytes out(need - 1);
+        std::cout << "short " << label << " | " << thrown([&] { f(std::span<uint8_t>(out)); }) << "\n";
+    };
+    small("chacha20_apply", 66, [&](std::span<uint8_t> o) { B::chacha20_apply(two(keys), two(nonces), in2, {}, o); });
+    small("aead_seal", 66, [&](std::span<uint8_t> o) { B::aead_seal(two(keys), two(nonces), in2, o, two(tags_out)); });
+    small("aead_open", 66, [&](std::span<uint8_t> o) {
+        B::aead_open(two(keys), two(nonces), in2, two(tags), o, std::span<uint8_t>(ok2));
+    });
+    small("wire_seal", 66 + 96, [&](std::span<uint8_t> o) { B::wire_seal(two(k32), two(nonces), in2, o); });
+    small("wire_open", 17, [&](std::span<uint8_t> o) { B::wire_open(two(k32), in2, o, std::span<uint8_t>(ok2)); });
+
+    // empty batches: an empty result, `ok` and reused output vectors left empty
+    auto dirty = [&] {
+        ok.assign(3, 7);
+        vv.assign(3, Bytes(4, 9));
+        sv.assign(3, B::Sealed{});
+    };
+    auto empty = [&](const char* label, auto&& f) {
+        dirty();
+        std::string r;
+        bool e = false;
+        r = thrown([&] { e = f(); });
+        std::cout << "empty " << label << " | " << (r == "no-throw" ? (e ? "empty" : "not-empty") : r) << "\n";
+    };
+    const std::span<const crypto::Key> nk;
+    const std::span<const crypto::Nonce> nn;
+    const std::span<const K32> n32;
+    const std::span<const ChunkId> nid;
+    const std::span<const uint32_t> nu32;
+    const std::span<const std::array<uint8_t, 16>> ntag;
+    empty("chacha20_apply/ret", [&] { return B::chacha20_apply(nk, nn, in0, {}).empty(); });
+    empty("chacha20_apply/vec", [&] { B::chacha20_apply(nk, nn, in0, {}, vv); return vv.empty(); });
+    empty("chacha20_apply/span", [&] { B::chacha20_apply(nk, nn, in0, {}, std::span<uint8_t>()); return true; });
+    empty("aead_seal/ret", [&] { return B::aead_seal(nk, nn, in0).empty(); });
+    empty("aead_seal/vec", [&] { B::aead_seal(nk, nn, in0, sv); return sv.empty(); });
+    empty("aead_seal/span", [&] { B::aead_seal(nk, nn, in0, std::span<uint8_t>(), {}); return true; });
+    empty("aead_open/ret", [&] { return B::aead_open(nk, nn, in0, ntag, ok).empty() && ok.empty(); });
+    empty("aead_open/vec", [&] { B::aead_open(nk, nn, in0, ntag, vv, ok); return vv.empty() && ok.empty(); });
+    empty("aead_open/span", [&] { B::aead_open(nk, nn, in0, ntag, std::span<uint8_t>(), std::span<uint8_t>()); return true; });
+    empty("sha256", [&] { return B::sha256(in0).empty(); });
+    empty("frame_seal", [&] { return B::frame_seal(n32, nn, in0).empty(); });
+    empty("frame_open", [&] { return B::frame_open(n32, nn, in0, ok).empty() && ok.empty(); });
+    empty("chunk_store", [&] { return B::chunk_store(nk, nn, in0, nid).empty(); });
+    empty("chunk_fetch", [&] { return B::chunk_fetch(nk, nn, nid, in0, n32, ok).empty() && ok.empty(); });
+    empty("shamir_split", [&] { return B::shamir_split(n32, 2, 3).empty(); });
+    empty("shamir_combine", [&] { return B::shamir_combine({}, 2, ok).empty() && ok.empty(); });
+    empty("chunk_store_shared", [&] { return B::chunk_store_shared(nn, in0, nid, 2, 3).empty(); });
+    empty("chunk_fetch_shared", [&] { return B::chunk_fetch_shared({}, 2, nn, nid, in0, n32, ok).empty() && ok.empty(); });
+    empty("wire_seal/ret", [&] { return B::wire_seal(n32, nn, in0).empty(); });
+    empty("wire_seal/vec", [&] { B::wire_seal(n32, nn, in0, vv); return vv.empty(); });
+    empty("wire_seal/span", [&] { B::wire_seal(n32, nn, in0, std::span<uint8_t>()); return true; });
+    empty("wire_open/ret", [&] { return B::wire_open(n32, in0, ok).empty() && ok.empty(); });
+    empty("wire_open/vec", [&] { B::wire_open(n32, in0, vv, ok); return vv.empty() && ok.empty(); });
+    empty("wire_open/span", [&] { B::wire_open(n32, in0, std::span<uint8_t>(), std::span<uint8_t>()); return true; });
+    empty("wire_seal_sessions", [&] { return B::wire_seal_sessions(two(k32), nu32, nn, in0).empty(); });
+    empty("wire_open_sessions", [&] { return B::wire_open_sessions(two(k32), nu32, in0, ok).empty() && ok.empty(); });
+    empty("chunk_frames_seal", [&] { return B::chunk_frames_seal(two(k32), nu32, nn, nid, nu32, in0).empty(); });
+    empty("chunk_frames_open", [&] { return B::chunk_frames_open(two(k32), nu32, in0, nid, nk, nn, n32).empty(); });
+    empty("pow_search", [&] { return B::pow_search(in0, {}, B::PowSchedule::Store, 10).empty(); });
+    empty("pow_check", [&] { return B::pow_check(in0, {}, {}).empty(); });
+    empty("session_keys", [&] { return B::session_keys(nk, {}, {}).empty(); });
+    empty("key_exchange", [&] {
+        const auto r = B::key_exchange(nu32, nu32);
+        return r.publics.empty() && r.secrets.empty();
+    });
+    empty("handshake_accept", [&] { return B::handshake_accept(PeerId{}, 7, 4, {}, {}).empty(); });
+    empty("compute_store_pow", [&] { return security::batch::compute_store_pow({}, 4, 10).empty(); });
+    empty("store_pow_valid", [&] { return security::batch::store_pow_valid({}, {}, 4).empty(); });
+
+    // the entry points without per-record arrays: what they return without the device
+    const auto p48 = B::packed_offsets(in2, 48), m48 = B::packed_offsets(in2, -48);
+    std::cout << "value packed_offsets |";
+    for (auto o : p48) std::cout << " " << o;
+    for (auto o : m48) std::cout << " " << o;
+    std::cout << "\n";
+    PeerId a{}, b{};
+    a[0] = 0xAA;
+    b[31] = 0xBB;
+    ChunkId cid{};
+    cid[1] = 0xCC;
+    const uint8_t shards[3] = {1, 2, 3};
+    std::cout << "value handshake_pow_prefix | " << hex(B::handshake_pow_prefix(a, b, 0x01020304u)) << "\n";
+    std::cout << "value announce_pow_prefix | " << hex(B::announce_pow_prefix(cid, a, "ep:1", "uri", shards, 258)) << "\n";
+    uint64_t nonce = 99;
+    bool found = B::compute_handshake_pow(a, b, 5, 0, nonce);  // difficulty 0: nonce 0, no search
+    std::cout << "value compute_handshake_pow | " << found << " " << nonce << "\n";
+    nonce = 99;
+    found = B::compute_announce_pow(cid, a, "ep:1", "uri", shards, 258, 0, nonce);
+    std::cout << "value compute_announce_pow | " << found << " " << nonce << "\n";
+    const auto free_pow = security::batch::compute_store_pow(two(work), 0, 10);
+    std::cout << "value compute_store_pow/0 | " << free_pow.size() << " " << (free_pow[0] && *free_pow[0] == 0) << "\n";
+    std::cout << "value store_pow_valid/0 | " << hex(security::batch::store_pow_valid(two(work), two(u64), 0)) << "\n";
+}
+
+static void be64(uint8_t* p, uint64_t x) {
+    for (int i = 0; i < 8; ++i) p[i] = (uint8_t)(x >> (56 - 8 * i));
+}
+
 int main() {
     std::string line;
     while (std::getline(std::cin, line)) {
@@ -390,6 +579,47 @@ int main() {
             for (auto& t : tags) tg.insert(tg.end(), t.begin(), t.end());
             std::cout << hex(ct) << " " << hex(tg) << " " << ao << " " << hex(pt) << " " << hex(frames) << " " << wo
                       << " " << hex(back) << " " << (same ? "1" : "0") << "\n";
+        } else if (op == "batch_args") {
+            batch_args();
+        } else if (op == "sha_batch") {
+            // crypto::batch::sha256 of the messages on the line; prints every digest, then 1/0:
+            // each equals enet_host_sha256 of the same message
+            std::vector<std::vector<uint8_t>> msgs;
+            for (std::string m; in >> m;) msgs.push_back(unhex(m));
+            std::vector<std::span<const uint8_t>> ms(msgs.begin(), msgs.end());
+            const auto got = crypto::batch::sha256(ms);
+            bool same = got.size() == msgs.size();
+            for (size_t i = 0; i < got.size(); ++i) {
+                std::array<uint8_t, 32> want{};
+                enet_host_sha256(msgs[i].data(), msgs[i].size(), want.data());
+                same = same && got[i] == want;
+                std::cout << hex(got[i]) << " ";
+            }
+            std::cout << (same ? "1" : "0") << "\n";
+        } else if (op == "session_keys") {
+            // crypto::batch::session_keys of 3 secrets with counters {0, 1, 2^40}; prints every key,
+            // then 1/0: each equals enet_host_hmac_sha256(secret, BE64(counter) || BE64(ticks))
+            std::string sec; int64_t t0 = 0; in >> sec >> t0;
+            const auto sb = unhex(sec);
+            crypto::Key secrets[3]{};
+            const uint64_t counters[3] = {0, 1, 1ull << 40};
+            const int64_t ticks[3] = {t0, t0 + 1, -t0};
+            for (int i = 0; i < 3; ++i) {
+                std::copy(sb.begin(), sb.end(), secrets[i].bytes.begin());
+                secrets[i].bytes[0] ^= (uint8_t)i;
+            }
+            const auto got = crypto::batch::session_keys(secrets, counters, ticks);
+            bool same = got.size() == 3;
+            for (size_t i = 0; i < got.size(); ++i) {
+                uint8_t m[16];
+                be64(m, counters[i]);
+                be64(m + 8, (uint64_t)ticks[i]);
+                std::array<uint8_t, 32> want{};
+                enet_host_hmac_sha256(secrets[i].bytes.data(), 32, m, 16, want.data());
+                same = same && got[i] == want;
+                std::cout << hex(got[i]) << " ";
+            }
+            std::cout << (same ? "1" : "0") << "\n";
         } else if (op == "fork_nonces") {
             // the frame nonce generator after fork(): parent and child each seal one frame (host
             // engine, FrameQueue::seal) from a generator that was in use before the fork; the

@@ -184,6 +184,80 @@ def test_cpp_frame_nonces_differ_after_fork(api_bin):
         assert flag == "1" and parent != child and len(parent) == len(child) == 24
 
 
+SIZE_CHECKED = [  # entry points with per-record arrays, by overload
+    "chacha20_apply/ret", "chacha20_apply/ret-counters", "chacha20_apply/vec", "chacha20_apply/span",
+    "aead_seal/ret", "aead_seal/vec", "aead_seal/span", "aead_open/ret", "aead_open/vec", "aead_open/span",
+    "frame_seal", "frame_open", "chunk_store", "chunk_fetch", "chunk_store_shared", "chunk_fetch_shared",
+    "wire_seal/ret", "wire_seal/vec", "wire_seal/span", "wire_open/ret", "wire_open/vec", "wire_open/span",
+    "wire_seal_sessions", "wire_open_sessions", "chunk_frames_seal", "chunk_frames_seal/versions",
+    "chunk_frames_open", "pow_search", "pow_check", "session_keys", "key_exchange", "store_pow_valid"]
+EMPTY_CHECKED = [e for e in SIZE_CHECKED if e not in ("chacha20_apply/ret-counters", "chunk_frames_seal/versions")] + [
+    "sha256", "shamir_split", "shamir_combine", "handshake_accept", "compute_store_pow"]
+
+
+def test_cpp_batch_argument_handling(api_bin):
+    """CPU, no device call: every crypto::batch / security::batch entry point throws
+    std::invalid_argument with its exact message for mismatched per-record array sizes and for a
+    contiguous output one byte short (records of 1 and 65 bytes), and returns empty -- `ok` and
+    reused output vectors emptied -- for an empty batch; the entry points without per-record
+    arrays return their host-computed values."""
+    res, _ = run_ops(api_bin, ["batch_args"])
+    got = {}
+    for line in res:
+        label, _, value = line.partition(" | ")
+        assert label not in got
+        got[label] = value
+    want = {}
+    for e in SIZE_CHECKED:
+        name = e.split("/")[0]
+        want[f"mismatch {e}"] = (f"enet {name}: size mismatch" if name == "store_pow_valid"
+                                 else f"enet batch::{name}: size mismatch")
+    for name in ("chacha20_apply", "aead_seal", "aead_open", "wire_seal", "wire_open"):
+        want[f"short {name}"] = f"enet batch::{name}: output span too small"
+    for e in EMPTY_CHECKED:
+        want[f"empty {e}"] = "empty"
+    be64 = lambda x: x.to_bytes(8, "big")
+    lp = lambda b: be64(len(b)) + b
+    a, b, cid = b"\xaa" + bytes(31), bytes(31) + b"\xbb", b"\x00\xcc" + bytes(30)
+    want["value packed_offsets"] = "0 49 162 0 0 17"
+    want["value handshake_pow_prefix"] = (lp(a) + lp(b) + be64(0x01020304)).hex()
+    want["value announce_pow_prefix"] = (lp(cid) + lp(a) + lp(b"ep:1") + lp(b"uri") + lp(b"\x01\x02\x03")
+                                         + be64(258)).hex()
+    want["value compute_handshake_pow"] = "1 0"
+    want["value compute_announce_pow"] = "1 0"
+    want["value compute_store_pow/0"] = "2 1"
+    want["value store_pow_valid/0"] = "0101"
+    assert got == want
+
+
+@pytest.mark.gpu
+def test_cpp_batch_sha256_blob_and_device_slot_paths(api_bin):
+    """crypto::batch::sha256 in one process: six messages around the padding boundaries (arena
+    under 8 KiB: the pinned zero-copy staging blob), then the same plus one of 8193 bytes (device
+    staging slots) -- bit-exact with the host engine and hashlib."""
+    msgs = [splitmix_bytes(9100 + L, L) for L in (0, 55, 56, 64, 119, 1000)]
+    long = msgs + [splitmix_bytes(9999, 8193)]
+    res, _ = run_ops(api_bin, ["sha_batch " + " ".join(h(m) for m in msgs),
+                               "sha_batch " + " ".join(h(m) for m in long)])
+    for line, ms in zip(res, (msgs, long)):
+        assert line.split() == [hashlib.sha256(m).hexdigest() for m in ms] + ["1"]
+
+
+@pytest.mark.gpu
+def test_cpp_batch_session_keys_vs_host_hmac(api_bin):
+    """crypto::batch::session_keys for 3 secrets, counters {0, 1, 2^40}: bit-exact with the host
+    engine's HMAC-SHA256(secret, BE64(counter) || BE64(ticks)) and Python's hmac."""
+    import hmac
+    sec, t0 = splitmix_bytes(4242, 32), 1234567890123
+    res, _ = run_ops(api_bin, [f"session_keys {sec.hex()} {t0}"])
+    want = []
+    for i, (c, t) in enumerate(zip((0, 1, 1 << 40), (t0, t0 + 1, -t0))):
+        key = bytes([sec[0] ^ i]) + sec[1:]
+        msg = c.to_bytes(8, "big") + (t % (1 << 64)).to_bytes(8, "big")
+        want.append(hmac.new(key, msg, hashlib.sha256).hexdigest())
+    assert res[0].split() == want + ["1"]
+
+
 @pytest.mark.gpu
 def test_cpp_api_matches_reference_golden(api_bin, golden):
     ops, expect = scalar_ops(golden, big=True)
