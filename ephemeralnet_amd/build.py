@@ -30,7 +30,7 @@ SOURCES = ["records.hip", "segments.hip", "stream.hip", "sha.hip", "pow.hip", "d
            "batch_staged.cpp", "pipeline.cpp", "host_engine.cpp",
            "frame_queue.cpp", "host_batch.cpp", "host_topo.cpp"]
 HEADERS = ["enet_device.hpp", "enet_internal.hpp", "long_route.hpp", "record_route.hpp", "long_records.hpp", "records_body.hpp",
-           "stream_common.hpp", "duplex_common.hpp", "host_engine.hpp", "scalar.hpp", "staging.hpp", "api_common.hpp", "host_batch.hpp", "host_topo.hpp", "gf256.hpp"]
+           "stream_common.hpp", "stream_map.hpp", "duplex_common.hpp", "host_engine.hpp", "scalar.hpp", "staging.hpp", "api_common.hpp", "host_batch.hpp", "host_topo.hpp", "gf256.hpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC",
           "-fvisibility=hidden", "-Wall", "-Wno-unused-function",
@@ -39,7 +39,7 @@ LDFLAGS = ["--offload-arch=gfx950", "-fPIC", "-shared"]
 
 
 DEVICE_HEADERS = ["enet_device.hpp", "enet_internal.hpp", "long_route.hpp", "record_route.hpp", "records_body.hpp", "stream_common.hpp",
-                  "duplex_common.hpp", "chacha_lockstep_asm.hpp", "gf256.hpp"]
+                  "stream_map.hpp", "duplex_common.hpp", "chacha_lockstep_asm.hpp", "gf256.hpp"]
 
 
 def _headers(src: str = "") -> list[str]:

@@ -3,7 +3,11 @@
 // Shape: every record is L bytes with L a multiple of 128*P (P = lanes per record), records
 // contiguous in both arenas (C2: 65 536 x 4 KiB, C4: 64 KiB chunks).  Lane j of record g owns
 // blocks [j*B, (j+1)*B), B = L/(64 P), and moves them in stages of two blocks (128 bytes per
-// lane, 8 KiB per wave).
+// lane, 8 KiB per wave).  Thread t of a workgroup of R = 512 / P records is lane t / R of record
+// t mod R (stream_map.hpp): lane j of every record sits in wave group j, so what one lane of a
+// record does for all of it -- the leader, j = 0: the one-time key, the AAD, the tag -- whole waves
+// skip on a scalar branch, and the leader's r, the other lanes' Poly1305 sums and open's verdict
+// cross through a small LDS exchange on the barriers S0(0), F1 and F2 that every wave meets anyway.
 //
 // One 768-thread workgroup per CU, two kinds of waves:
 //   * 8 compute waves (two per SIMD, the records' 512 lanes) run the keystream in the lockstep
@@ -26,7 +30,7 @@
 // Hand-offs use the shared barriers: the stage barrier S0 (inputs landed: the memory waves wait
 // for their DMAs before it; outputs of the previous stage written: the compute waves drain
 // their LDS writes before it) and keystream barrier 0 (the compute waves have read their inputs,
-// so the slab may be refilled).  LDS: 2 x 64 KiB.
+// so the slab may be refilled).  LDS: 2 x 64 KiB, and up to 15 KiB of exchange (AEAD, P > 1).
 // The LDS chunk swizzle sw(o) = ((o >> 1) & 7) ^ ((o & 1) << 2) makes the own-run ds_read_b128
 // (lane groups of 16: (sw, o & 1) distinct) and ds_write_b128 (8 contiguous lanes: sw distinct)
 // conflict-free (PMC SQ_LDS_BANK_CONFLICT = 0); the lane-linear DMA landing and store reads are
@@ -40,8 +44,11 @@
 // for MODE_XOR; RFC 8439 AEAD (no reference implementation) for seal / open.
 #include "record_route.hpp"
 #include "stream_common.hpp"
+#include "stream_map.hpp"
 
 namespace enet {
+
+static_assert(kMapLanes == kStreamLanes && kMapRun == kRun, "stream_map.hpp and the streaming kernel disagree");
 
 // Memory-wave schedule, in keystream barrier positions (an op at position k runs between barriers
 // k-1 and k; a step is ~276 shader cycles of compute, a 1 KiB DMA or store costs its memory
@@ -126,12 +133,22 @@ __global__ __launch_bounds__(kStreamWG) void stream_kernel(RecParams p) {
     // waves, stored by the memory waves); wave w's part is 8 KiB at 8 KiB w
     __shared__ __attribute__((aligned(16))) uint8_t s_in[kStreamLanes * kRun];
     __shared__ __attribute__((aligned(16))) uint8_t s_out[kStreamLanes * kRun];
+    // what the lanes of a record hand each other (AEAD, P > 1), record q of the workgroup's R:
+    // its leader's clamped r for the other lanes (written before S0(0), read after it), every
+    // other lane's scaled Poly1305 limbs for the leader (limb i of thread t at 512 i + t; before
+    // F1, after it), the leader's verdict for the tamper zeroing (open; before F2, after it)
+    constexpr uint32_t kRecs = kStreamLanes >> LOGP;  // R
+    constexpr bool kXch = kPoly && P > 1;
+    __shared__ uint4 s_r[kXch ? kRecs : 1];
+    __shared__ uint32_t s_limb[kXch ? 5 * kStreamLanes : 1];
+    __shared__ uint32_t s_bad[kXch && MODE == MODE_OPEN ? kRecs : 1];
 
     const uint32_t L = (uint32_t)p.uniform_len;
     const bool compute = threadIdx.x < kStreamLanes;
-    const uint32_t gid = blockIdx.x * kStreamLanes + (compute ? threadIdx.x : 0u);
-    const uint32_t rec = gid >> LOGP;  // the launch covers records [0, n), n = whole workgroups
-    const uint32_t j = gid & (P - 1);
+    // the launch covers records [0, n), n = whole workgroups; lane j of every record sits in wave
+    // group j (stream_map.hpp), j == 0 is the record's leader
+    const StreamLane me = stream_lane(LOGP, blockIdx.x, compute ? threadIdx.x : 0u);
+    const uint32_t rec = me.rec;
     // probe (dbg 16384, tools/stage_probe.py): compute wave 0 stamps the 100 MHz clock and the
     // shader clock at entry, the shader clock at the body start, after every stage barrier S0 and
     // after F1, and both clocks at exit, into the workgroup's tag slots
@@ -166,6 +183,9 @@ __global__ __launch_bounds__(kStreamWG) void stream_kernel(RecParams p) {
 
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    // the record-lane, taken from the wave's first thread where a wave holds one value of it
+    // (P <= 8): a scalar, so whole waves branch around what only some lane of a record does
+    const uint32_t j = P == 1 ? 0u : LOGP <= 3 ? stream_lane(LOGP, blockIdx.x, 64u * wave).j : me.j;
     const uint32_t B = L >> (6 + LOGP);  // blocks per lane (the host launches L % (128 P) == 0)
     const uint32_t S = B >> 1;           // stages
     const bool mem = !(dbg & 1);
@@ -173,40 +193,27 @@ __global__ __launch_bounds__(kStreamWG) void stream_kernel(RecParams p) {
     if (!compute) {
         // ================================================================ memory waves
         // Memory wave m serves compute waves 2m and 2m+1.  Instruction i of compute wave c moves
-        // 16-byte chunk kk ^ sw(o) of its owner o = 8i + lane/8; the arena offset is
-        // off(c, i) = off(c, i & 1) + (i >> 1) * (16 / P) * L (owner o's record advances by 8/P
-        // per instruction for P <= 8 and by one per two for P = 16; its lane within the record and
-        // sw(o) ^ sw(o mod 16) only alternate).  32-bit offsets from the arena bases: the host
-        // launches this kernel only for arenas < 4 GiB.
+        // 16-byte chunk kk ^ sw(o) of its owner o = 8i + lane/8, thread 64c + o of the workgroup.
+        // 32-bit offsets from the arena bases: the host launches this kernel only for arenas
+        // < 4 GiB.
         const uint32_t m = wave - 8u;
         const uint32_t kk = lane & 7u;
         // the memory waves win issue arbitration: their one instruction per keystream barrier
         // interval then never waits behind the compute waves' VALU stream (C2: +1-2 %,
         // tools/prio_ab.sh 876/879/889 -> 893/896/899 GiB/s on one box)
         if (!(dbg & 4096)) __builtin_amdgcn_s_setprio(ISS.prio_mem);
-        uint32_t offA[2], offAB[2];
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const uint32_t wg0 = blockIdx.x * kStreamLanes + (2u * m + c) * 64u;
-            uint32_t o2[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const uint32_t o = 8u * i + (lane >> 3);
-                const uint32_t go = wg0 + o;
-                o2[i] = (go >> LOGP) * L + (((go & (P - 1)) * B) << 6) + 16u * (kk ^ slab_sw(o));
-            }
-            offA[c] = o2[0];
-            offAB[c] = o2[1] - o2[0];
-        }
         // every slot's lane offset precomputed (16 VGPRs): a memory wave shares its SIMD with two
         // compute waves that keep the VALU saturated, so each VALU instruction it issues waits for
         // a slot -- the address arithmetic of a store (~10 VALU) held it ~300 cycles past the
         // next barrier (tools/stream_probe.py trace).  Slots are SALU + VMEM / LDS only.
-        const uint32_t offD = (16u >> LOGP) * L;
+        // The owner's record and record-lane come from the map the compute waves use
+        // (stream_map.hpp; consecutive owners are consecutive records, L bytes apart).
         uint32_t offs[16];
 #pragma unroll
-        for (int s = 0; s < 16; ++s)
-            offs[s] = offA[s >> 3] + (uint32_t)(s & 1) * offAB[s >> 3] + (uint32_t)((s & 7) >> 1) * offD;
+        for (int s = 0; s < 16; ++s) {
+            const uint32_t t = stream_mem_owner(m, s, lane);
+            offs[s] = stream_lane_offset(LOGP, L, stream_lane(LOGP, blockIdx.x, t)) + 16u * (kk ^ slab_sw(t & 63u));
+        }
         // the arena bases are SGPR operands of the DMA / store asm: keep them provably uniform
         auto uni = [](const void* q) {
             const uint64_t v = reinterpret_cast<uintptr_t>(q);
@@ -325,16 +332,15 @@ __global__ __launch_bounds__(kStreamWG) void stream_kernel(RecParams p) {
         rt0 = __builtin_amdgcn_s_memrealtime();
     }
 
-    // ---- Poly1305: one-time key from block 0 (runs while stage 0 lands); lane 0 absorbs the AAD
+    // ---- Poly1305: the record's leader makes the one-time key from block 0 (while stage 0 lands),
+    // hands r to the record's other lanes and absorbs the AAD; waves without a leader go straight
+    // to the stage barrier
     uint32_t h[5] = {0, 0, 0, 0, 0};
     PolyR32 PR{};
     uint32_t pad[4] = {0, 0, 0, 0};
     uint32_t na = 0, aad_len = 0;
+    const uint32_t q = threadIdx.x & (kRecs - 1u);  // the record's place in the workgroup
     if (kPoly) {
-        uint32_t otk[16];
-        chacha_block(R, 0u, otk);
-        PR = polyr32_make(otk[0], otk[1], otk[2], otk[3]);
-        pad[0] = otk[4]; pad[1] = otk[5]; pad[2] = otk[6]; pad[3] = otk[7];
         uint64_t aoff = 0;
         if (p.aad) {
             aoff = p.aad_off[rec];
@@ -342,6 +348,11 @@ __global__ __launch_bounds__(kStreamWG) void stream_kernel(RecParams p) {
         }
         na = (aad_len + 15) >> 4;
         if (j == 0) {
+            uint32_t otk[16];
+            chacha_block(R, 0u, otk);
+            PR = polyr32_make(otk[0], otk[1], otk[2], otk[3]);
+            pad[0] = otk[4]; pad[1] = otk[5]; pad[2] = otk[6]; pad[3] = otk[7];
+            if (kXch) s_r[q] = make_uint4(PR.r0, PR.r1, PR.r2, PR.r3);
             for (uint32_t s = 0; s < na; ++s) {
                 const uint8_t* ap = p.aad + aoff + 16ull * s;
                 const uint32_t cnt = min(16u, aad_len - 16u * s);
@@ -368,11 +379,15 @@ __global__ __launch_bounds__(kStreamWG) void stream_kernel(RecParams p) {
     } else {
         if constexpr (ISS.prio_old != 0) __builtin_amdgcn_s_setprio(ISS.prio_old);
     }
-    for (uint32_t st = 0; st < S; ++st) {
-        // S0(st): the memory waves saw stage st land; this wave's output writes are done
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        stream_barrier();
-        if (__builtin_expect(stamp, 0)) stamps[3 + st] = __builtin_amdgcn_s_memtime();
+    // S0(0): the memory waves saw stage 0 land; the leaders' r is in the exchange
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    stream_barrier();
+    if (__builtin_expect(stamp, 0)) stamps[3] = __builtin_amdgcn_s_memtime();
+    if (kXch && j != 0) {
+        const uint4 r = s_r[q];
+        PR = polyr32_make(r.x, r.y, r.z, r.w);
+    }
+    for (uint32_t st = 0;;) {  // (S >= 1: the host launches L >= 128 P)
         uint8_t* myrun = s_in + threadIdx.x * kRun;
         // the run is read now and consumed after the keystream, so its LDS latency is hidden
         uint32_t w[32];
@@ -459,6 +474,38 @@ __global__ __launch_bounds__(kStreamWG) void stream_kernel(RecParams p) {
                 *reinterpret_cast<uint4*>(myout + 16u * (k ^ msw)) =
                     make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
         }
+        if (kPoly) {
+            // the stage's Poly1305 stays in front of the stage barrier (with the loop's exit in its
+            // middle the compiler moved seal's behind it, between S0 and keystream barrier 0)
+#pragma unroll
+            for (int i = 0; i < 5; ++i) ENET_PIN(h[i]);
+        }
+        if (++st == S) break;
+        // S0(st): the memory waves saw stage st land; this wave's output writes are done
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        stream_barrier();
+        if (__builtin_expect(stamp, 0)) stamps[3 + st] = __builtin_amdgcn_s_memtime();
+    }
+    // ---- Poly1305 tail, the part of every lane: the length block LE64(|aad|) || LE64(|ct|) in the
+    // record's last lane; every other lane scales its sum by r^e, e = N-1-s_last (the last wave
+    // group skips the power), and hands the leader its limbs
+    uint32_t l[5] = {0, 0, 0, 0, 0};
+    if (kPoly) {
+        const uint32_t nct = L >> 4;
+        const uint32_t N = na + nct + 1;
+        if (j == P - 1) poly32_block(h, PR, aad_len, 0u, L, 0u, 1u);
+        h32_to_limbs(h, l);
+        if (j != P - 1) {
+            const uint32_t e = N - 1 - (na + 4 * (j + 1) * B - 1);  // >= 4 B + 1
+            uint32_t r26[5], xx[5];
+            plimbs(r26, PR.r0, PR.r1, PR.r2, PR.r3);
+            ppow(r26, e, xx);
+            pmul(l, pmul_make(xx));
+        }
+        if (kXch && j != 0) {
+#pragma unroll
+            for (int i = 0; i < 5; ++i) s_limb[kStreamLanes * i + threadIdx.x] = l[i];
+        }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     stream_barrier();  // F1
@@ -480,41 +527,32 @@ __global__ __launch_bounds__(kStreamWG) void stream_kernel(RecParams p) {
     }
     uint32_t diff = 0;
     if (kPoly) {
-        // length block LE64(|aad|) || LE64(|ct|), owned by the last lane of the record
-        const uint32_t nct = L >> 4;
-        const uint32_t N = na + nct + 1;
-        uint32_t e = 0;  // contribution scale: r^(N-1-s_last)
-        if (j == P - 1) poly32_block(h, PR, aad_len, 0u, L, 0u, 1u);
-        else e = N - 1 - (na + 4 * (j + 1) * B - 1);
-        uint32_t l[5];
-        h32_to_limbs(h, l);
-        if (P > 1) {
-            if (e > 0) {
-                uint32_t r26[5], xx[5];
-                plimbs(r26, PR.r0, PR.r1, PR.r2, PR.r3);
-                ppow(r26, e, xx);
-                pmul(l, pmul_make(xx));
-            }
+        // the leader's part: the sum of the record's lanes, the tag, and for open the verdict,
+        // handed to the record's other lanes across F2
+        if (j == 0) {
+            if (kXch) {
 #pragma unroll
-            for (uint32_t o = P >> 1; o >= 1; o >>= 1) {
+                for (uint32_t jj = 1; jj < P; ++jj) {
 #pragma unroll
-                for (int i = 0; i < 5; ++i) l[i] += __shfl_xor(l[i], (int)o);
+                    for (int i = 0; i < 5; ++i) l[i] += s_limb[kStreamLanes * i + stream_thread(LOGP, q, jj)];
+                }
             }
-        }
-        uint32_t tag[4];
-        pfinish(l, pad, tag);
-        if (MODE == MODE_SEAL) {
-            if (j == 0) {
+            uint32_t tag[4];
+            pfinish(l, pad, tag);
+            if (MODE == MODE_SEAL) {
                 uint32_t* tp = reinterpret_cast<uint32_t*>(p.tag_out + 16ull * rec);
                 tp[0] = tag[0]; tp[1] = tag[1]; tp[2] = tag[2]; tp[3] = tag[3];
+            } else {
+                const uint32_t* tp = reinterpret_cast<const uint32_t*>(p.tag_in + 16ull * rec);
+                diff = (tag[0] ^ tp[0]) | (tag[1] ^ tp[1]) | (tag[2] ^ tp[2]) | (tag[3] ^ tp[3]);
+                p.ok[rec] = diff == 0 ? 1 : 0;
+                if (kXch) s_bad[q] = diff;
             }
-        } else {
-            const uint32_t* tp = reinterpret_cast<const uint32_t*>(p.tag_in + 16ull * rec);
-            diff = (tag[0] ^ tp[0]) | (tag[1] ^ tp[1]) | (tag[2] ^ tp[2]) | (tag[3] ^ tp[3]);
-            if (j == 0) p.ok[rec] = diff == 0 ? 1 : 0;
         }
+        if (kXch && MODE == MODE_OPEN) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
     stream_barrier();  // F2: the memory waves' stores of this workgroup are complete
+    if (kXch && MODE == MODE_OPEN && j != 0) diff = s_bad[q];
     if (MODE == MODE_OPEN && diff != 0) {
         // authentication failed: do not release plaintext
         uint8_t* seg = p.out + o0 + (uint64_t)rec * L + ((uint64_t)j * B << 6);
