@@ -7,6 +7,7 @@ import hashlib
 import json
 import os
 import platform
+import re
 import subprocess
 import sys
 import time
@@ -28,9 +29,10 @@ SOURCES = ["records.hip", "segments.hip", "stream.hip", "sha.hip", "pow.hip", "d
            "shamir.hip", "shamir_host.cpp", "handshake.hip",
            "capi.cpp", "long_records.cpp", "chunk_hybrid.cpp", "staging.cpp", "scalar_api.cpp", "batch_records.cpp",
            "batch_staged.cpp", "pipeline.cpp", "host_engine.cpp",
-           "frame_queue.cpp", "host_batch.cpp", "host_topo.cpp"]
+           "frame_queue.cpp", "queue_core.cpp", "host_batch.cpp", "host_topo.cpp"]
 HEADERS = ["enet_device.hpp", "enet_internal.hpp", "long_route.hpp", "record_route.hpp", "long_records.hpp", "records_body.hpp",
-           "stream_common.hpp", "stream_map.hpp", "duplex_common.hpp", "host_engine.hpp", "scalar.hpp", "staging.hpp", "api_common.hpp", "host_batch.hpp", "host_topo.hpp", "gf256.hpp"]
+           "stream_common.hpp", "stream_map.hpp", "duplex_common.hpp", "host_engine.hpp", "scalar.hpp", "staging.hpp", "api_common.hpp", "host_batch.hpp", "host_topo.hpp", "gf256.hpp",
+           "queue_knobs.hpp", "wire_host.hpp", "queue_slots.hpp", "queue_core.hpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC",
           "-fvisibility=hidden", "-Wall", "-Wno-unused-function",
@@ -57,16 +59,29 @@ def _obj(src: str, obj_dir: str = OBJ) -> str:
     return os.path.join(obj_dir, os.path.splitext(src)[0] + ".o")
 
 
-def tools_tus(probes: bool = False) -> list[str]:
-    """TUs the tools build compiles with -DENET_TOOLS_BUILD (the others are the product's)."""
-    out = []
-    for f in SOURCES:
-        if f.endswith(".hip") and not probes:
+def _reads_tools_macro(src: str) -> bool:
+    """Does csrc/src, or a csrc header it includes (transitively), read ENET_TOOLS_BUILD?"""
+    todo, seen = [src], set()
+    while todo:
+        f = todo.pop()
+        if f in seen:
             continue
-        with open(os.path.join(CSRC, f)) as fh:
-            if "ENET_TOOLS_BUILD" in fh.read():
-                out.append(f)
-    return out
+        seen.add(f)
+        try:
+            with open(os.path.join(CSRC, f)) as fh:
+                text = fh.read()
+        except OSError:  # a system or include/ header
+            continue
+        if "ENET_TOOLS_BUILD" in text:
+            return True
+        todo += re.findall(r'^\s*#\s*include\s*"([^"]+)"', text, re.M)
+    return False
+
+
+def tools_tus(probes: bool = False) -> list[str]:
+    """TUs the tools build compiles with -DENET_TOOLS_BUILD (the others are the product's): those
+    that read the macro themselves or through a header of csrc/ (queue_knobs.hpp)."""
+    return [f for f in SOURCES if (probes or not f.endswith(".hip")) and _reads_tools_macro(f)]
 
 
 def source_digest(tools: bool = False) -> str:

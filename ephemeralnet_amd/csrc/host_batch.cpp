@@ -521,18 +521,6 @@ AutoRates probe_mode(int dev) {
 bool via_copies(Mode m) { return m != Mode::ZeroCopy; }  // SDMA H2D (up), kernels, [D2H (down)]
 bool zc_out(Mode m) { return m == Mode::SdmaInZcOut; }    // kernels write host memory, no D2H
 
-// ENET_HOST_TRACE=1: one stderr line per job with where its wall time went (diagnosis)
-bool trace_on() {
-    static const bool v = [] {
-        const char* e = std::getenv("ENET_HOST_TRACE");
-        return e && e[0] == '1';
-    }();
-    return v;
-}
-double now_s() {
-    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
 #ifdef ENET_TOOLS_BUILD
 // tools build only (A/B of the pipeline shape): ENET_HOST_SLOTS, ENET_HOST_CHUNK_MIB, ENET_HOST_RAMP
 uint64_t env_u64(const char* name, uint64_t dflt) {

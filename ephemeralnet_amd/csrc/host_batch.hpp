@@ -18,12 +18,26 @@
 // gather / scatter copies: the device stage works on them in place.
 #pragma once
 
+#include <chrono>
 #include <cstddef>
 #include <cstdint>
+#include <cstdlib>
 #include <span>
 #include <vector>
 
 namespace enet::hb {
+
+// ENET_HOST_TRACE=1: one stderr line per job / per queue with where its wall time went (diagnosis)
+inline bool trace_on() {
+    static const bool v = [] {
+        const char* e = std::getenv("ENET_HOST_TRACE");
+        return e && e[0] == '1';
+    }();
+    return v;
+}
+inline double now_s() {
+    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
 
 enum class Op : int {
     Xor,           // ChaCha20::apply (counters: start counter per record, nullable = 0)

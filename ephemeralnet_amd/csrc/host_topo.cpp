@@ -143,6 +143,31 @@ std::vector<int> node_cpus(int node) {
     return parse_cpulist(read_file("/sys/devices/system/node/node" + std::to_string(node) + "/cpulist"));
 }
 
+// The L3 domains from sysfs: cpuN/cache/indexK with level 3 names its domain by id; the ids are
+// made dense in order of first appearance
+const std::vector<int>& l3_of_cpu() {
+    static const std::vector<int> v = [] {
+        std::vector<int> out, ids;
+        const long ncpu = sysconf(_SC_NPROCESSORS_CONF);
+        for (long c = 0; c < ncpu && c < 4096; ++c) {
+            int dense = -1;
+            for (int idx = 0; idx < 6 && dense < 0; ++idx) {
+                const std::string dir =
+                    "/sys/devices/system/cpu/cpu" + std::to_string(c) + "/cache/index" + std::to_string(idx);
+                long long level = 0, id = -1;
+                if (!parse_int(read_file(dir + "/level"), level) || level != 3) continue;
+                if (!parse_int(read_file(dir + "/id"), id) || id < 0) continue;
+                const auto it = std::find(ids.begin(), ids.end(), (int)id);
+                dense = (int)(it - ids.begin());
+                if (it == ids.end()) ids.push_back((int)id);
+            }
+            out.push_back(dense);
+        }
+        return out;
+    }();
+    return v;
+}
+
 std::vector<int> allowed_cpus() {
     std::vector<int> out;
     const int max_cpus = 8192;

@@ -42,6 +42,7 @@ Plan plan(const std::vector<int>& node_cpus, const std::vector<int>& allowed, ui
 // facts of this machine / process
 int device_numa_node(int device);   // -1 unknown (no sysfs entry, single-node machine)
 std::vector<int> node_cpus(int node);
+const std::vector<int>& l3_of_cpu();  // dense L3-domain (CCD) index of every CPU, -1 unknown; read once
 std::vector<int> allowed_cpus();     // sched_getaffinity of the calling thread
 uint32_t cgroup_quota_cpus();        // 0 = unlimited / unknown
 uint32_t env_cpus();                 // ENET_HOST_CPUS, 0 = unset

@@ -1,7 +1,7 @@
 // scalar.hpp -- routing state of the scalar C++ drop-in (enet_crypto.h "scalar"), shared by the
 // translation units that serve reference signatures.  Defined in scalar_api.cpp, beside the per-call
-// hot paths that read it (HmacSha256::compute, Sha256::digest, ChaCha20::apply); frame_queue.cpp
-// reads it too.
+// hot paths that read it (HmacSha256::compute, Sha256::digest, ChaCha20::apply); the frame queues
+// (frame_queue.cpp, queue_core.cpp) read it too.
 #pragma once
 
 #include <atomic>

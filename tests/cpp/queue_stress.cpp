@@ -4,6 +4,7 @@
 // usage: queue_stress <policy auto|device|host> <threads> <frames per thread> <seed>
 //        queue_stress nonces <policy> <threads> <frames per thread>: every thread seals that many
 //        empty messages under ONE shared key; prints how many of the nonces were distinct
+//        queue_stress async | window | split | tickets ...: see each mode's comment below
 // Phase 1: every thread seals its own session's messages (lengths 0..3000, some 64 KiB, one
 // frame of the 1 MiB maximum payload per run) through ONE shared FrameQueue.  Phase 2: every
 // thread opens its own frames through ONE shared FrameReceiveQueue, with every 7th frame
@@ -12,7 +13,11 @@
 // own messages.  Prints a sample of (key, message, frame) lines for the oracle check in
 // tests/test_frame_queue.py and a summary line.
 #include <algorithm>
+#include <array>
+#include <chrono>
 #include <condition_variable>
+#include <memory>
+#include <optional>
 #include <deque>
 #include <mutex>
 #include <atomic>
@@ -316,7 +321,241 @@ int split_mode(const std::string& policy, int F, int W) {
     return (bad || mismatch) ? 1 : 0;
 }
 
+// tickets <policy> <threads> <frames>: the FrameTicket paths no other mode takes -- ready(), a
+// ticket dropped uncollected (three ways), view() twice and get() after it, a ticket that
+// outlives its queue, an empty ticket.  Every thread runs `frames` messages of its own session
+// through ONE shared FrameQueue with kTicketWindow in flight, then the frames it collected through
+// ONE shared FrameReceiveQueue (every 5th tampered).  Then, one thread at a time: a burst of kBurst
+// frames all dropped, a window of kAfterDrop collected (AUTO must route it to the host engine
+// again: the dropped tickets left the thread's backlog), and kOutlive frames each way through
+// queues destroyed before their tickets are collected.
+namespace {
+
+constexpr int kTicketWindow = 64, kBurst = 2000, kAfterDrop = 16, kOutlive = 200;
+
+struct TicketCounts {
+    std::atomic<int> bad{0}, mismatch{0}, collected{0}, dropped{0}, opened{0}, rejected{0};
+    std::atomic<unsigned long long> tx_submitted{0}, rx_submitted{0}, burst_host{0}, after_drop_host{0};
+};
+
+// Items [0, n) through submit(k) with kTicketWindow in flight.  By item: k % 3 == 1 is dropped --
+// k % 9 == 1 by its destructor straight after the submission (before its pass can have run), 4 by
+// release() once ready(), 7 by a fresh ticket move-assigned over it; k % 3 == 0 is polled with
+// ready(), then get(); k % 3 == 2 is viewed twice, then get().  check(k, result) judges every
+// collected result.
+template <class Submit, class Check>
+void ticket_window(int n, Submit submit, Check check, TicketCounts& c) {
+    std::deque<std::pair<int, FrameTicket>> q;
+    int next = 0;
+    auto fresh = [&](int& k) -> FrameTicket {
+        while (next < n) {
+            k = next++;
+            FrameTicket t = submit(k);
+            if (k % 9 != 1) return t;
+            ++c.dropped;  // ~FrameTicket here
+        }
+        k = -1;
+        return FrameTicket();
+    };
+    for (;;) {
+        while ((int)q.size() < kTicketWindow) {
+            int k;
+            FrameTicket t = fresh(k);
+            if (k < 0) break;
+            q.emplace_back(k, std::move(t));
+        }
+        if (q.empty()) break;
+        const int k = q.front().first;
+        FrameTicket& t = q.front().second;
+        if (k % 3 == 1 && k % 9 == 4) {
+            while (!t.ready()) std::this_thread::yield();
+            t.release();
+            if (t.valid() || t.ready()) ++c.bad;
+            ++c.dropped;
+        } else if (k % 3 == 1) {
+            int k2;
+            t = fresh(k2);  // over the live ticket (an empty one once every item is submitted)
+            ++c.dropped;
+            if (k2 >= 0) q.emplace_back(k2, std::move(t));
+        } else if (k % 3 == 0) {
+            while (!t.ready()) std::this_thread::yield();
+            auto r = t.get();
+            if (t.valid()) ++c.bad;
+            ++c.collected;
+            check(k, r);
+        } else {
+            std::span<const std::uint8_t> a, b;
+            const bool oka = t.view(a), okb = t.view(b);
+            if (oka != okb || a.data() != b.data() || a.size() != b.size() || (!oka && !a.empty())) ++c.bad;
+            const std::vector<std::uint8_t> seen(a.begin(), a.end());
+            if (!t.ready()) ++c.bad;
+            auto r = t.get();
+            if (t.valid() || (bool)r != oka || (r && *r != seen)) ++c.bad;
+            ++c.collected;
+            check(k, r);
+        }
+        q.pop_front();
+    }
+}
+
+// kOutlive items through a queue made by make_queue() and destroyed before their tickets are
+// collected; every 4th is viewed, judged and released while the queue lives (Batch.hpp: release
+// every view before the queue is destroyed), the others get() after it
+template <class MakeQueue, class Item, class Check>
+void outlive_queue(MakeQueue make_queue, Item item, Check check, TicketCounts& c) {
+    std::vector<FrameTicket> held;
+    {
+        auto q = make_queue();
+        for (int i = 0; i < kOutlive; ++i) held.push_back(q->submit(item(i).first, item(i).second));
+        for (int i = 0; i < kOutlive; i += 4) {
+            std::span<const std::uint8_t> v;
+            std::optional<std::vector<std::uint8_t>> r;
+            if (held[i].view(v)) r.emplace(v.begin(), v.end());
+            else if (!v.empty()) ++c.bad;
+            held[i].release();
+            check(i, r);
+        }
+    }
+    for (int i = 0; i < kOutlive; ++i) {
+        if (i % 4 == 0) {
+            if (held[i].valid()) ++c.bad;
+            continue;
+        }
+        if (!held[i].valid()) ++c.bad;
+        check(i, held[i].get());
+    }
+}
+
+}  // namespace
+
+int tickets_mode(const std::string& policy, int T, int F) {
+    enet_scalar_set_policy(policy == "device" ? ENET_SCALAR_DEVICE : policy == "host" ? ENET_SCALAR_HOST
+                                                                                      : ENET_SCALAR_AUTO, 0);
+    FrameQueueOptions opt;
+    if (const char* e = std::getenv("QUEUE_STRESS_MAX_FRAMES")) opt.max_frames = (std::size_t)std::atoll(e);
+    FrameQueue tx(opt);
+    FrameReceiveQueue rx(opt);
+    TicketCounts c;
+    std::atomic<int> arrived{0};
+    std::mutex serial;
+    std::vector<std::thread> th;
+    for (int t = 0; t < T; ++t)
+        th.emplace_back([&, t] {
+            std::uint64_t s = 555 + (std::uint64_t)t;
+            std::array<std::uint8_t, 32> key{};
+            for (auto& b : key) b = (std::uint8_t)splitmix(s);
+            std::vector<std::vector<std::uint8_t>> msgs(F), frames(F);
+            for (int i = 0; i < F; ++i) {
+                msgs[i].resize(i % 4 ? splitmix(s) % 1700 : 1500);
+                for (auto& b : msgs[i]) b = (std::uint8_t)splitmix(s);
+            }
+            {  // an empty ticket
+                FrameTicket e;
+                std::vector<std::uint8_t> out(3, 1);
+                std::span<const std::uint8_t> v(out);
+                if (e.valid() || e.ready() || e.get()) ++c.bad;
+                if (e.get(out) || !out.empty()) ++c.bad;
+                if (e.view(v) || !v.empty()) ++c.bad;
+                e.release();
+            }
+            auto sealed_ok = [&](const std::vector<std::uint8_t>& m, const std::optional<std::vector<std::uint8_t>>& f) {
+                if (f && !frame_mismatch(key, m, *f)) return true;
+                ++(f ? c.mismatch : c.bad);
+                return false;
+            };
+            ticket_window(
+                F,
+                [&](int k) {
+                    ++c.tx_submitted;
+                    return tx.submit(key, msgs[k]);
+                },
+                [&](int k, std::optional<std::vector<std::uint8_t>> f) {
+                    if (sealed_ok(msgs[k], f)) frames[k] = std::move(*f);
+                },
+                c);
+            // ... and every collected frame opened the same way, every 5th with a body or MAC byte flipped
+            std::vector<int> got;
+            for (int i = 0; i < F; ++i)
+                if (!frames[i].empty()) got.push_back(i);
+            auto tampered = [](int j) { return j % 5 == 2; };
+            auto opened_ok = [&](bool expect, const std::vector<std::uint8_t>& m,
+                                 const std::optional<std::vector<std::uint8_t>>& r) {
+                if (r) ++c.opened;
+                else ++c.rejected;
+                if ((bool)r != expect || (r && *r != m)) ++c.bad;
+            };
+            ticket_window(
+                (int)got.size(),
+                [&](int j) {
+                    auto f = frames[got[j]];
+                    if (tampered(j)) f[16 + (std::size_t)j % (f.size() - 16)] ^= 0x04;
+                    ++c.rx_submitted;
+                    return rx.submit(key, f);
+                },
+                [&](int j, std::optional<std::vector<std::uint8_t>> m) { opened_ok(!tampered(j), msgs[got[j]], m); }, c);
+            // the rest one thread at a time, so that the queue's counters move for this thread only
+            ++arrived;
+            while (arrived.load() < T) std::this_thread::yield();
+            std::lock_guard<std::mutex> lk(serial);
+            const std::vector<std::uint8_t> small(64, (std::uint8_t)t);
+            const auto h0 = tx.stats().host_flushes;
+            std::vector<FrameTicket> burst;
+            for (int i = 0; i < kBurst; ++i) burst.push_back(tx.submit(key, small));
+            const auto h1 = tx.stats().host_flushes;
+            for (int i = 0; i < kBurst; i += 2) burst[i].release();
+            burst.clear();  // the odd ones by their destructors
+            c.tx_submitted += kBurst;
+            c.dropped += kBurst;
+            const auto h2 = tx.stats().host_flushes;
+            for (int i = 0; i < kAfterDrop; ++i) burst.push_back(tx.submit(key, msgs[i % F]));
+            for (int i = 0; i < kAfterDrop; ++i) sealed_ok(msgs[i % F], burst[i].get());
+            c.tx_submitted += kAfterDrop;
+            c.collected += kAfterDrop;
+            c.burst_host += h1 - h0;
+            c.after_drop_host += tx.stats().host_flushes - h2;
+            // tickets that outlive their queue
+            std::vector<std::vector<std::uint8_t>> wire(kOutlive);
+            outlive_queue([&] { return std::make_unique<FrameQueue>(opt); },
+                          [&](int i) { return std::make_pair(key, std::span<const std::uint8_t>(msgs[i % F])); },
+                          [&](int i, std::optional<std::vector<std::uint8_t>> f) {
+                              if (sealed_ok(msgs[i % F], f)) wire[i] = std::move(*f);
+                          },
+                          c);
+            for (int i = 0; i < kOutlive; ++i)
+                if (wire[i].empty()) wire[i].assign(48, 0);  // counted bad above; keep the shape
+                else if (tampered(i)) wire[i][16 + (std::size_t)i % (wire[i].size() - 16)] ^= 0x04;
+            outlive_queue([&] { return std::make_unique<FrameReceiveQueue>(opt); },
+                          [&](int i) { return std::make_pair(key, std::span<const std::uint8_t>(wire[i])); },
+                          [&](int i, std::optional<std::vector<std::uint8_t>> m) {
+                              opened_ok(!tampered(i), msgs[i % F], m);
+                          },
+                          c);
+        });
+    for (auto& x : th) x.join();
+    // a dropped ticket's pass may still be running: its frames are counted when it has run
+    auto st = tx.stats(), sr = rx.stats();
+    for (int i = 0; i < 5000 && (st.frames < c.tx_submitted || sr.frames < c.rx_submitted); ++i) {
+        std::this_thread::sleep_for(std::chrono::milliseconds(1));
+        st = tx.stats(), sr = rx.stats();
+    }
+    enet_scalar_stats ss{};
+    enet_scalar_get_stats(&ss);
+    std::printf("summary bad=%d mismatch=%d collected=%d dropped=%d opened=%d rejected=%d tx_submitted=%llu "
+                "rx_submitted=%llu tx_frames=%llu tx_flushes=%llu tx_host_flushes=%llu rx_frames=%llu rx_flushes=%llu "
+                "rx_host_flushes=%llu burst_host=%llu after_drop_host=%llu evicted=%llu device_failures=%llu\n",
+                c.bad.load(), c.mismatch.load(), c.collected.load(), c.dropped.load(), c.opened.load(),
+                c.rejected.load(), c.tx_submitted.load(), c.rx_submitted.load(), (unsigned long long)st.frames,
+                (unsigned long long)st.flushes, (unsigned long long)st.host_flushes, (unsigned long long)sr.frames,
+                (unsigned long long)sr.flushes, (unsigned long long)sr.host_flushes, c.burst_host.load(),
+                c.after_drop_host.load(), (unsigned long long)(st.evicted + sr.evicted),
+                (unsigned long long)ss.device_failures);
+    return (c.bad || c.mismatch || st.frames != c.tx_submitted || sr.frames != c.rx_submitted) ? 1 : 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc > 1 && std::string(argv[1]) == "tickets")
+        return tickets_mode(argc > 2 ? argv[2] : "device", argc > 3 ? std::atoi(argv[3]) : 8,
+                            argc > 4 ? std::atoi(argv[4]) : 600);
     if (argc > 1 && std::string(argv[1]) == "window")
         return window_mode(argc > 2 ? argv[2] : "device", argc > 3 ? std::atoi(argv[3]) : 16,
                            argc > 4 ? std::atoi(argv[4]) : 256, argc > 5 ? std::atoi(argv[5]) : 4000);

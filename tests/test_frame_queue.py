@@ -20,26 +20,43 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "queue_stress.cpp")
 
 
+def compile_against(lib, src, out):
+    """Build a test program from `src` against the library file `lib`."""
+    name = os.path.basename(lib)[len("lib"):-len(".so")]
+    subprocess.run(["g++", "-std=c++20", "-O2", "-pthread", "-I", os.path.join(ROOT, "include"), src, "-o", out,
+                    "-L", os.path.dirname(lib), "-l" + name, "-Wl,-rpath," + os.path.dirname(lib)], check=True)
+    return out
+
+
 @pytest.fixture(scope="module")
 def stress_bin(tmp_path_factory):
     from ephemeralnet_amd import build as B
-    lib = B.build(verbose=False)
-    out = str(tmp_path_factory.mktemp("q") / "queue_stress")
-    subprocess.run(["g++", "-std=c++20", "-O2", "-pthread", "-I", os.path.join(ROOT, "include"), SRC, "-o",
-                    out, "-L", os.path.dirname(lib), "-lenet_crypto", "-Wl,-rpath," + os.path.dirname(lib)],
-                   check=True)
-    return out
+    return compile_against(B.build(verbose=False), SRC, str(tmp_path_factory.mktemp("q") / "queue_stress"))
+
+
+@pytest.fixture(scope="module")
+def tools_stress_bin(tmp_path_factory):
+    """queue_stress over the tools build (stand-in device, stall hook, A/B knobs); skips when that
+    build is missing or stale."""
+    from ephemeralnet_amd import build as B
+    stamp = B.read_stamp(B.LIB_TOOLS)
+    if not os.path.exists(B.LIB_TOOLS) or not stamp or stamp.get("sources_sha256") != B.source_digest(tools=True):
+        pytest.skip("tools build (ephemeralnet_amd/libenet_crypto_tools.so) missing or stale")
+    return compile_against(B.LIB_TOOLS, SRC, str(tmp_path_factory.mktemp("qt") / "queue_stress_tools"))
+
+
+def summary(r):
+    """The k=v pairs of a queue_stress run's summary line."""
+    summ = [ln for ln in r.stdout.splitlines() if ln.startswith("summary")]
+    assert summ, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    return {k: int(v) for k, v in (kv.split("=") for kv in summ[0].split()[1:])}
 
 
 def run(stress_bin, policy, threads=16, frames=150, seed=1):
     r = subprocess.run([stress_bin, policy, str(threads), str(frames), str(seed)], capture_output=True,
                        text=True, timeout=600)
-    lines = r.stdout.splitlines()
-    summ = [ln for ln in lines if ln.startswith("summary")]
-    assert summ, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
-    s = dict(kv.split("=") for kv in summ[0].split()[1:])
-    s = {k: int(v) for k, v in s.items()}
-    sample = [ln.split()[1:] for ln in lines if ln.startswith("frame ")]
+    s = summary(r)
+    sample = [ln.split()[1:] for ln in r.stdout.splitlines() if ln.startswith("frame ")]
     return r.returncode, s, sample, r.stderr
 
 
@@ -147,10 +164,7 @@ def test_queues_512_blocking_session_threads_on_gpu(stress_bin, policy):
 def run_async(stress_bin, policy, threads=8, frames=400):
     r = subprocess.run([stress_bin, "async", policy, str(threads), str(frames)], capture_output=True, text=True,
                        timeout=600)
-    summ = [ln for ln in r.stdout.splitlines() if ln.startswith("summary")]
-    assert summ, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
-    s = {k: int(v) for k, v in (kv.split("=") for kv in summ[0].split()[1:])}
-    return r.returncode, s, r.stderr
+    return r.returncode, summary(r), r.stderr
 
 
 def check_async(rc, s, threads, frames):
@@ -187,10 +201,7 @@ def test_queues_async_on_gpu(stress_bin):
 def run_window(stress_bin, policy, threads=16, window=256, frames=4000):
     r = subprocess.run([stress_bin, "window", policy, str(threads), str(window), str(frames)], capture_output=True,
                        text=True, timeout=600)
-    summ = [ln for ln in r.stdout.splitlines() if ln.startswith("summary")]
-    assert summ, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
-    s = {k: int(v) for k, v in (kv.split("=") for kv in summ[0].split()[1:])}
-    return r.returncode, s, r.stderr
+    return r.returncode, summary(r), r.stderr
 
 
 def check_window(rc, s, threads, frames):
@@ -273,11 +284,7 @@ def test_queue_bench_passes_and_rate_on_gpu(tmp_path):
     workers take passes a little earlier (910-1 016 frames measured) and the rate must stay
     >= 8 M frames/s each way.  Rates and CPU per frame are printed."""
     from ephemeralnet_amd import build as B
-    lib = B.build(verbose=False)
-    out = str(tmp_path / "queue_bench")
-    subprocess.run(["g++", "-std=c++20", "-O2", "-pthread", "-I", os.path.join(ROOT, "include"), BENCH_SRC, "-o",
-                    out, "-L", os.path.dirname(lib), "-lenet_crypto", "-Wl,-rpath," + os.path.dirname(lib)],
-                   check=True)
+    out = compile_against(B.build(verbose=False), BENCH_SRC, str(tmp_path / "queue_bench"))
     import json
     for inflight in ("4", None):
         args = [out, "device", "reuse", "16", "1024", "1.0"] + (["1500", inflight] if inflight else [])
@@ -293,27 +300,18 @@ def test_queue_bench_passes_and_rate_on_gpu(tmp_path):
             assert d["seal_frames_per_s"] >= 8e6 and d["open_frames_per_s"] >= 8e6, d
 
 
-def test_device_style_passes_and_evictions_on_cpu(tmp_path):
+def test_device_style_passes_and_evictions_on_cpu(tools_stress_bin):
     """The queue's device path on a CPU-only host: the tools build's stand-in device
     (ENET_QUEUE_FAKE_US: a pass takes 100 us; ENET_QUEUE_FAKE_COMPUTE: the worker computes it on
     the host engine first) runs every pass as a device pass.  16 threads x 4 096 frames in flight
     reference more passes than the queue keeps, so finished passes are evicted into their tickets
     while other threads collect, drop and reuse slots (generation-tagged slot words); every frame
     is still checked byte for byte and every tamper rejected."""
-    from ephemeralnet_amd import build as B
-    stamp = B.read_stamp(B.LIB_TOOLS)
-    if not os.path.exists(B.LIB_TOOLS) or not stamp or stamp.get("sources_sha256") != B.source_digest(tools=True):
-        pytest.skip("tools build (ephemeralnet_amd/libenet_crypto_tools.so) missing or stale")
-    out = str(tmp_path / "queue_stress_tools")
-    subprocess.run(["g++", "-std=c++20", "-O2", "-pthread", "-I", os.path.join(ROOT, "include"), SRC, "-o", out,
-                    "-L", os.path.dirname(B.LIB_TOOLS), "-lenet_crypto_tools",
-                    "-Wl,-rpath," + os.path.dirname(B.LIB_TOOLS)], check=True)
     env = dict(os.environ, ENET_QUEUE_FAKE_US="100", ENET_QUEUE_FAKE_COMPUTE="1")
-    r = subprocess.run([out, "window", "device", "16", "4096", "5000"], capture_output=True, text=True,
+    r = subprocess.run([tools_stress_bin, "window", "device", "16", "4096", "5000"], capture_output=True, text=True,
                        timeout=600, env=env)
-    summ = [ln for ln in r.stdout.splitlines() if ln.startswith("summary")]
-    assert r.returncode == 0 and summ, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
-    s = {k: int(v) for k, v in (kv.split("=") for kv in summ[0].split()[1:])}
+    s = summary(r)
+    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
     print(s)
     assert s["bad"] == 0 and s["tx_frames"] == 16 * 5000 and s["rx_frames"] == 16 * 5000
     assert s["tx_host_flushes"] == 0 and s["rx_host_flushes"] == 0 and s["device_failures"] == 0
@@ -321,44 +319,23 @@ def test_device_style_passes_and_evictions_on_cpu(tmp_path):
 
 
 @pytest.mark.gpu
-def test_queues_staged_passes_on_gpu(tmp_path):
+def test_queues_staged_passes_on_gpu(tools_stress_bin):
     """Device passes with their input side staged in device memory (one SDMA copy, the kernel
     reading HBM, the results written straight into the pinned pass -- the default for passes of
     640+ frames sealing, 512+ opening): forced on every pass through the tools build
     (ENET_QUEUE_STAGE=1), the window stress run checks every frame byte for byte and every tamper rejected, with no host
     flush and no device failure."""
-    from ephemeralnet_amd import build as B
-    stamp = B.read_stamp(B.LIB_TOOLS)
-    if not os.path.exists(B.LIB_TOOLS) or not stamp or stamp.get("sources_sha256") != B.source_digest(tools=True):
-        pytest.skip("tools build (ephemeralnet_amd/libenet_crypto_tools.so) missing or stale")
-    out = str(tmp_path / "queue_stress_tools")
-    subprocess.run(["g++", "-std=c++20", "-O2", "-pthread", "-I", os.path.join(ROOT, "include"), SRC, "-o", out,
-                    "-L", os.path.dirname(B.LIB_TOOLS), "-lenet_crypto_tools",
-                    "-Wl,-rpath," + os.path.dirname(B.LIB_TOOLS)], check=True)
     env = dict(os.environ, ENET_QUEUE_STAGE="1")
-    r = subprocess.run([out, "window", "device", "16", "256", "1500"], capture_output=True, text=True,
+    r = subprocess.run([tools_stress_bin, "window", "device", "16", "256", "1500"], capture_output=True, text=True,
                        timeout=300, env=env)
-    summ = [ln for ln in r.stdout.splitlines() if ln.startswith("summary")]
-    assert r.returncode == 0 and summ, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
-    s = {k: int(v) for k, v in (kv.split("=") for kv in summ[0].split()[1:])}
+    s = summary(r)
+    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
     print(s)
     check_window(r.returncode, s, 16, 1500)
     assert s["tx_host_flushes"] == 0 and s["rx_host_flushes"] == 0 and s["device_failures"] == 0, s
 
 
-def tools_stress_bin(tmp_path):
-    from ephemeralnet_amd import build as B
-    stamp = B.read_stamp(B.LIB_TOOLS)
-    if not os.path.exists(B.LIB_TOOLS) or not stamp or stamp.get("sources_sha256") != B.source_digest(tools=True):
-        pytest.skip("tools build (ephemeralnet_amd/libenet_crypto_tools.so) missing or stale")
-    out = str(tmp_path / "queue_stress_tools")
-    subprocess.run(["g++", "-std=c++20", "-O2", "-pthread", "-I", os.path.join(ROOT, "include"), SRC, "-o", out,
-                    "-L", os.path.dirname(B.LIB_TOOLS), "-lenet_crypto_tools",
-                    "-Wl,-rpath," + os.path.dirname(B.LIB_TOOLS)], check=True)
-    return out
-
-
-def test_stalled_overflow_submitter_on_cpu(tmp_path):
+def test_stalled_overflow_submitter_on_cpu(tools_stress_bin):
     """a submitter whose reservation found its pass full and that is then
     preempted must not close the pass's NEXT generation (reopened meanwhile, possibly for another
     shard): that left the new owner's open pointer on a closed pass.  The fix ties close_full to
@@ -369,42 +346,123 @@ def test_stalled_overflow_submitter_on_cpu(tmp_path):
     its close while passes are evicted and reopened; every frame is checked byte for byte.  (The
     stale close did not hang here before the fix either: eviction churn soon reopens the pass for
     some shard, which re-validates the dangling pointer -- the fix is by construction.)"""
-    out = tools_stress_bin(tmp_path)
     env = dict(os.environ, ENET_QUEUE_FAKE_US="20", ENET_QUEUE_FAKE_COMPUTE="1", ENET_QUEUE_STALL_OVERFLOW_US="300",
                ENET_QUEUE_SHARDS="2", ENET_QUEUE_SHARD_BY="thread", QUEUE_STRESS_MAX_FRAMES="64")
-    r = subprocess.run([out, "window", "device", "16", "128", "3000"], capture_output=True, text=True,
+    r = subprocess.run([tools_stress_bin, "window", "device", "16", "128", "3000"], capture_output=True, text=True,
                        timeout=120, env=env)
-    summ = [ln for ln in r.stdout.splitlines() if ln.startswith("summary")]
-    assert r.returncode == 0 and summ, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
-    s = {k: int(v) for k, v in (kv.split("=") for kv in summ[0].split()[1:])}
+    s = summary(r)
+    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
     print(s)
     check_window(r.returncode, s, 16, 3000)
     assert s["overflows"] > 1000 and s["evicted"] > 0, s
 
 
-def test_split_submitter_collector_auto_stays_on_host_on_cpu(tmp_path):
+def test_split_submitter_collector_auto_stays_on_host_on_cpu(tools_stress_bin):
     """one reader thread submits, one writer thread collects, at most 8 frames
     between them, policy auto with a (stand-in) device.  The frames are counted against the
     submitting thread only until collected -- on the other thread -- so the trickle never reaches
     AUTO's device threshold (320): every frame on the host engine, every byte checked."""
-    out = tools_stress_bin(tmp_path)
     env = dict(os.environ, ENET_QUEUE_FAKE_US="60", ENET_QUEUE_FAKE_COMPUTE="1")
-    r = subprocess.run([out, "split", "auto", "3000", "8"], capture_output=True, text=True, timeout=300, env=env)
-    summ = [ln for ln in r.stdout.splitlines() if ln.startswith("summary")]
-    assert r.returncode == 0 and summ, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
-    s = {k: int(v) for k, v in (kv.split("=") for kv in summ[0].split()[1:])}
+    r = subprocess.run([tools_stress_bin, "split", "auto", "3000", "8"], capture_output=True, text=True, timeout=300, env=env)
+    s = summary(r)
+    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
     print(s)
     assert s["bad"] == 0 and s["mismatch"] == 0
     assert s["tx_frames"] == 3000 and s["tx_host_flushes"] == s["tx_flushes"] == 3000, s
 
 
-def test_split_submitter_collector_device_on_cpu(tmp_path):
+def test_split_submitter_collector_device_on_cpu(tools_stress_bin):
     """The same split under the device policy (stand-in device): the frames go through passes and
     come back byte for byte to the collecting thread."""
-    out = tools_stress_bin(tmp_path)
     env = dict(os.environ, ENET_QUEUE_FAKE_US="60", ENET_QUEUE_FAKE_COMPUTE="1")
-    r = subprocess.run([out, "split", "device", "2000", "64"], capture_output=True, text=True, timeout=300, env=env)
-    summ = [ln for ln in r.stdout.splitlines() if ln.startswith("summary")]
-    assert r.returncode == 0 and summ, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
-    s = {k: int(v) for k, v in (kv.split("=") for kv in summ[0].split()[1:])}
+    r = subprocess.run([tools_stress_bin, "split", "device", "2000", "64"], capture_output=True, text=True, timeout=300, env=env)
+    s = summary(r)
+    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
     assert s["bad"] == 0 and s["mismatch"] == 0 and s["tx_frames"] == 2000 and s["tx_host_flushes"] == 0, s
+
+
+def run_tickets(binary, policy, threads, frames, **env):
+    r = subprocess.run([binary, "tickets", policy, str(threads), str(frames)], capture_output=True, text=True,
+                       timeout=300, env=dict(os.environ, **env))
+    return r.returncode, summary(r), r.stderr
+
+
+def check_tickets(rc, s, threads, frames):
+    """queue_stress tickets: per thread every third item is dropped (destructor, release() after
+    ready(), move-assignment), the others are collected after ready() or through view() + get();
+    the collected frames are opened the same way (every 5th tampered); then 2 000 frames all
+    dropped, 16 collected, and 200 each way through queues destroyed before their tickets."""
+    assert rc == 0 and s["bad"] == 0 and s["mismatch"] == 0, s
+    dropped = lambda n: sum(1 for k in range(n) if k % 3 == 1)
+    sealed = frames - dropped(frames)  # frames collected from the send queue = frames opened
+    assert s["tx_submitted"] == threads * (frames + 2000 + 16) and s["rx_submitted"] == threads * sealed, s
+    # every submitted frame is served, collected or not
+    assert s["tx_frames"] == s["tx_submitted"] and s["rx_frames"] == s["rx_submitted"], s
+    assert s["dropped"] == threads * (dropped(frames) + dropped(sealed) + 2000), s
+    assert s["collected"] == threads * (sealed + sealed - dropped(sealed) + 16), s
+    rejected = sum(1 for j in range(sealed) if j % 3 != 1 and j % 5 == 2) + sum(1 for i in range(200) if i % 5 == 2)
+    assert s["rejected"] == threads * rejected, s
+    assert s["opened"] == threads * (sealed - dropped(sealed) + 200 - rejected), s
+
+
+def test_tickets_host_engine(stress_bin):
+    """FrameTicket::ready(), dropped tickets, view() twice + get(), tickets outliving their queue
+    and the empty ticket under the host policy: every ticket is born with its result."""
+    rc, s, _ = run_tickets(stress_bin, "host", 8, 600)
+    check_tickets(rc, s, 8, 600)
+    assert s["tx_host_flushes"] == s["tx_flushes"] == s["tx_frames"] and s["device_failures"] == 0, s
+    assert s["burst_host"] == 8 * 2000 and s["after_drop_host"] == 8 * 16, s
+
+
+@pytest.mark.parametrize("policy", ["device", "auto"])
+def test_tickets_device_style_passes_on_cpu(tools_stress_bin, policy):
+    """The same through device-style passes (the tools build's stand-in device computing on the
+    host engine), passes of 16 slots so that dropped and half-collected passes must be reused and
+    evicted for the run to finish.  auto: each thread's burst reaches the device queue once it
+    holds 320 uncollected frames, and after dropping all of them its next 16 frames are served by
+    the host engine again -- exactly 16 host flushes per thread: the dropped tickets left AUTO's
+    backlog."""
+    rc, s, _ = run_tickets(tools_stress_bin, policy, 8, 600, ENET_QUEUE_FAKE_US="60", ENET_QUEUE_FAKE_COMPUTE="1",
+                           QUEUE_STRESS_MAX_FRAMES="64")
+    print(s)
+    check_tickets(rc, s, 8, 600)
+    assert s["device_failures"] == 0 and s["evicted"] > 0, s
+    if policy == "device":
+        assert s["tx_host_flushes"] == 0 and s["rx_host_flushes"] == 0 and s["after_drop_host"] == 0, s
+    else:
+        assert s["after_drop_host"] == 8 * 16, s
+        assert s["burst_host"] <= 8 * 320 and s["tx_flushes"] > s["tx_host_flushes"], s
+
+
+@pytest.mark.gpu
+def test_tickets_on_gpu(stress_bin):
+    """4 threads x 64 in flight x 500 frames, policy device: several passes per shard and slots
+    reused across generations on the MI355X; no host flush, no device failure."""
+    rc, s, err = run_tickets(stress_bin, "device", 4, 500)
+    print(s)
+    check_tickets(rc, s, 4, 500)
+    assert s["tx_host_flushes"] == 0 and s["rx_host_flushes"] == 0 and s["device_failures"] == 0, err
+    assert s["tx_flushes"] < s["tx_frames"], s
+
+
+def test_tools_build_compiles_every_unit_behind_the_knobs_header():
+    """The tools-build hooks live in csrc/queue_knobs.hpp: every unit that includes it, directly or
+    through another header, is among the units compiled with -DENET_TOOLS_BUILD (a unit left out
+    would link the product's empty inlines into the tools library) and no kernel is; and the tools
+    library's stamp records each of those units as built with that flag, naming nothing else as
+    recompiled."""
+    from ephemeralnet_amd import build as B
+    tus = B.tools_tus()
+    assert {"frame_queue.cpp", "queue_core.cpp", "capi.cpp", "host_batch.cpp"} <= set(tus), tus
+    assert not [f for f in tus if f.endswith(".hip")], tus
+    for f in B.SOURCES:  # the selection is the text search of every unit's include closure
+        text = open(os.path.join(B.CSRC, f)).read()
+        if f.endswith(".cpp") and ("ENET_TOOLS_BUILD" in text or '#include "queue_core.hpp"' in text):
+            assert f in tus, f
+    stamp = B.read_stamp(B.LIB_TOOLS)
+    if not os.path.exists(B.LIB_TOOLS) or not stamp or stamp.get("sources_sha256") != B.source_digest(tools=True):
+        pytest.skip("tools build (ephemeralnet_amd/libenet_crypto_tools.so) missing or stale")
+    for f in tus:
+        assert stamp["tu_sha256"][f] == B.tu_digest(f, tools=True), f  # flags + source + headers
+        assert stamp["tu_sha256"][f] != B.tu_digest(f, tools=False), f
+    assert set(stamp["recompiled"]) <= set(tus), stamp["recompiled"]

@@ -129,6 +129,7 @@ DESC = {
     "r05t_pytest_queue.log": "frame-queue GPU tests with backlog routing",
     "r05w_queue_bench_host_tail.jsonl": "frame queue host engine vs device after the host ChaCha20 tail went vector",
     "r05w_scalar_latency_auto.jsonl": "scalar-signature latency (policy auto) with the vector ChaCha20 tail",
+    "frame_queue_split_ab.jsonl": "tools/queue_bench against the library before and after the frame_queue.cpp split, alternately, six pairs per case (device reuse 16 x 1 024, device view 16 x 256, host view 16 x 256, host sync 16)",
     "r05w_bench.json": "bench line incl. the frame_queue side leg",
     "r05y_bench_repeat_one_box.jsonl": "the default bench line five times on one box (value, kernel ms, power)",
     "r05z2_queue_bench_hmac_cache.jsonl": "frame queue host engine vs device with the HMAC pad cache",
