@@ -19,6 +19,10 @@ Operations mirror the reference src/crypto API, batched (ShardianLabs/EphemeralN
                   src/core/Node.cpp:1872-1926, src/network/KeyExchange.cpp:9-48
   session_rotate KeyManager::rotate_if_needed over a SessionTable  src/network/KeyManager.cpp:56-92
   key_exchange   KeyExchange::compute_public / derive_shared_secret src/network/KeyExchange.cpp:22-48
+  chunk_frame_seal/open a stored chunk's Chunk message as a session frame, and back
+                  src/core/Node.cpp:1254-1297, 1615-1677, src/protocol/Message.cpp:204-246
+  announce_frame_seal/open compute_announce_pow + encode_signed + frame, and handle_announce's admission
+                  src/core/Node.cpp:155-230, 2332-2357, 2512-2661, src/protocol/Message.cpp:215-235
 """
 from __future__ import annotations
 
@@ -77,10 +81,35 @@ EXPORTS = [
     "enet_host_unregister", "enet_shamir_split_batch", "enet_shamir_combine_batch",
     "enet_handshake_accept_batch", "enet_session_rotate_batch", "enet_key_exchange_batch",
     "enet_chunk_frame_seal_batch", "enet_chunk_frame_open_batch",
+    "enet_announce_frame_seal_batch", "enet_announce_frame_open_batch",
 ]
 
 # status of chunk_frame_open (enet_crypto.h): the first failed check
 ENET_CF_OK, ENET_CF_FRAME, ENET_CF_HEADER, ENET_CF_CHUNK_ID, ENET_CF_HASH = 0, 1, 2, 3, 4
+
+# status of announce_frame_seal / announce_frame_open (enet_crypto.h): the first failed check
+ENET_AF_OK, ENET_AF_FRAME, ENET_AF_HEADER, ENET_AF_SENDER, ENET_AF_NO_MANIFEST, ENET_AF_POW = 0, 1, 2, 3, 4, 5
+NODE_POW_ATTEMPTS = 500_000  # kMaxAnnouncePowAttempts, src/core/Node.cpp:40
+
+
+class _AnnounceFields(C.Structure):
+    _fields_ = [
+        ("manifests", C.c_uint32),
+        ("chunk_ids", C.c_void_p),
+        ("uris", C.c_void_p),
+        ("uri_offsets", C.c_void_p),
+        ("manifest", C.c_void_p),
+        ("endpoints", C.c_uint32),
+        ("endpoint_bytes", C.c_void_p),
+        ("endpoint_offsets", C.c_void_p),
+        ("endpoint", C.c_void_p),
+        ("shards", C.c_void_p),
+        ("shard_offsets", C.c_void_p),
+        ("peer_id", C.c_void_p),
+        ("ttl", C.c_void_p),
+        ("versions", C.c_void_p),
+    ]
+
 
 # verdicts of handshake_accept (enet_crypto.h)
 ENET_HS_BAD_PUBLIC, ENET_HS_OK, ENET_HS_BAD_POW, ENET_HS_BAD_SLOT = 0, 1, 2, 3
@@ -235,6 +264,8 @@ def lib() -> C.CDLL:
         L.enet_key_exchange_batch.argtypes = [u32, vp, vp, vp, vp, vp]
         L.enet_chunk_frame_seal_batch.argtypes = [rp, vp, u32, vp, vp, vp, vp, vp]
         L.enet_chunk_frame_open_batch.argtypes = [rp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.enet_announce_frame_seal_batch.argtypes = [rp, vp, u32, vp, C.POINTER(_AnnounceFields), u32, u64, vp, vp, vp]
+        L.enet_announce_frame_open_batch.argtypes = [rp, vp, u32, vp, vp, u32, vp, vp, vp]
         for name in EXPORTS:
             getattr(L, name)
         _lib = L
@@ -477,6 +508,67 @@ def chunk_frame_open(b: Batch, out, out_offsets, chunk_ids, chunk_keys, chunk_no
                                              _ptr(chunk_keys), _ptr(chunk_nonces), _ptr(chunk_hashes),
                                              _ptr(data_out), _ptr(ttl_out), _ptr(status), _stream(stream)),
            "enet_chunk_frame_open_batch")
+
+
+@dataclass
+class AnnounceFields:
+    """enet_announce_fields over device tensors: M manifests (chunk_ids uint8 [M,32], uris uint8 arena,
+    uri_offsets int64 [M+1]), Ep endpoints (endpoint_bytes, endpoint_offsets int64 [Ep+1]), per-record
+    shard lists (shards, shard_offsets int64 [n+1]), the local peer_id uint8 [32], ttl int32 [n]
+    (uint32 bits), and the optional index tables manifest / endpoint int32 [n] (None: record i takes
+    manifest i / endpoint i) and versions uint8 [n] (None: 4; clamped to 1..4)."""
+    chunk_ids: "object"
+    uris: "object"
+    uri_offsets: "object"
+    endpoint_bytes: "object"
+    endpoint_offsets: "object"
+    shards: "object"
+    shard_offsets: "object"
+    peer_id: "object"
+    ttl: "object"
+    manifest: "object" = None
+    endpoint: "object" = None
+    versions: "object" = None
+
+    def struct(self) -> _AnnounceFields:
+        f = _AnnounceFields()
+        f.manifests = int(self.uri_offsets.numel()) - 1
+        f.endpoints = int(self.endpoint_offsets.numel()) - 1
+        f.chunk_ids, f.uris, f.uri_offsets = _ptr(self.chunk_ids), _ptr(self.uris), _ptr(self.uri_offsets)
+        f.endpoint_bytes, f.endpoint_offsets = _ptr(self.endpoint_bytes), _ptr(self.endpoint_offsets)
+        f.shards, f.shard_offsets = _ptr(self.shards), _ptr(self.shard_offsets)
+        f.peer_id, f.ttl = _ptr(self.peer_id), _ptr(self.ttl)
+        f.manifest, f.endpoint, f.versions = _ptr(self.manifest), _ptr(self.endpoint), _ptr(self.versions)
+        return f
+
+
+def announce_frame_seal(b: Batch, out, out_offsets, fields: AnnounceFields, difficulty: int, work_nonce, status,
+                        max_attempts: int = NODE_POW_ATTEMPTS, session=None, sessions=0, mid=None, stream=None) -> None:
+    """Gossip send (Node::deliver_manifest): out_i = the wire frame of the Announce message built from
+    `fields`, |out_i| = 130 + E + U + A (+ 8 for a v4 record, which carries work_nonce[i]).  b.arena /
+    b.offsets are not read (b.offsets only gives the batch size); b.nonces = the frame nonces, b.keys
+    the session keys (per record, or the table with `session` int32 [n] / `sessions` / `mid`).  At
+    difficulty > 0 the v4 records' proof of work is searched first (compute_announce_pow, at most
+    max_attempts candidates); max_attempts = 0: work_nonce int64 [n] is input.  status uint8 [n] =
+    ENET_AF_OK / ENET_AF_FRAME / ENET_AF_POW; a failed record's slot and nonce are zero."""
+    r = b.records(out, out_offsets)
+    f = fields.struct()
+    _check(lib().enet_announce_frame_seal_batch(C.byref(r), _ptr(session), sessions, _ptr(mid), C.byref(f),
+                                                int(difficulty), int(max_attempts), _ptr(work_nonce), _ptr(status),
+                                                _stream(stream)), "enet_announce_frame_seal_batch")
+
+
+def announce_frame_open(b: Batch, out, out_offsets, peer_ids, difficulty: int, info, status, session=None,
+                        sessions=0, mid=None, stream=None) -> None:
+    """Gossip receive (decode_signed -> handle_announce): b.arena holds received wire frames (nonces
+    come from the frames), b.keys the session keys as in announce_frame_seal, peer_ids uint8 [n,32]
+    the sessions' peers.  out_i = the message (|in_i| - 48 bytes), info int32 [n,8] = version, ttl,
+    E, U, A, nonce low, nonce high, 0; status uint8 [n] = ENET_AF_*: the first failed check; a failed
+    record's message and info are zero."""
+    r = b.records(out, out_offsets)
+    _check(lib().enet_announce_frame_open_batch(C.byref(r), _ptr(session), sessions, _ptr(mid), _ptr(peer_ids),
+                                                int(difficulty), _ptr(info), _ptr(status), _stream(stream)),
+           "enet_announce_frame_open_batch")
 
 
 def pow_search(prefixes, offsets, difficulty, schedule: int, max_attempts: int, nonces, found,

@@ -25,13 +25,13 @@ OBJ = os.path.join(PKG, "build")
 LIB_TOOLS = os.path.join(PKG, "libenet_crypto_tools.so")
 OBJ_TOOLS = os.path.join(PKG, "build_tools")
 SOURCES = ["records.hip", "segments.hip", "stream.hip", "sha.hip", "pow.hip", "duplex.hip", "duplex_split.hip",
-           "chunk_frames.hip",
+           "chunk_frames.hip", "announce_frames.hip",
            "shamir.hip", "shamir_host.cpp", "handshake.hip",
            "capi.cpp", "long_records.cpp", "chunk_hybrid.cpp", "staging.cpp", "scalar_api.cpp", "batch_records.cpp",
            "batch_staged.cpp", "pipeline.cpp", "host_engine.cpp",
            "frame_queue.cpp", "queue_core.cpp", "host_batch.cpp", "host_topo.cpp"]
 HEADERS = ["enet_device.hpp", "enet_internal.hpp", "long_route.hpp", "record_route.hpp", "long_records.hpp", "records_body.hpp",
-           "stream_common.hpp", "stream_map.hpp", "duplex_common.hpp", "host_engine.hpp", "scalar.hpp", "staging.hpp", "api_common.hpp", "host_batch.hpp", "host_topo.hpp", "gf256.hpp",
+           "stream_common.hpp", "stream_map.hpp", "duplex_common.hpp", "pow_common.hpp", "host_engine.hpp", "scalar.hpp", "staging.hpp", "api_common.hpp", "host_batch.hpp", "host_topo.hpp", "gf256.hpp",
            "queue_knobs.hpp", "wire_host.hpp", "queue_slots.hpp", "queue_core.hpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC",
@@ -41,7 +41,7 @@ LDFLAGS = ["--offload-arch=gfx950", "-fPIC", "-shared"]
 
 
 DEVICE_HEADERS = ["enet_device.hpp", "enet_internal.hpp", "long_route.hpp", "record_route.hpp", "records_body.hpp", "stream_common.hpp",
-                  "stream_map.hpp", "duplex_common.hpp", "chacha_lockstep_asm.hpp", "gf256.hpp"]
+                  "stream_map.hpp", "duplex_common.hpp", "pow_common.hpp", "chacha_lockstep_asm.hpp", "gf256.hpp"]
 
 
 def _headers(src: str = "") -> list[str]:

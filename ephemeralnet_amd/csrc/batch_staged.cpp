@@ -1,6 +1,6 @@
 // batch_staged.cpp -- the crypto::batch and security::batch calls (Batch.hpp, StoreProof.hpp) that
 // drive the C ABI themselves over the calling thread's staging (staging.hpp): SHA-256, Shamir key
-// shares and the chunk steps that carry them, chunk transfer frames, proof of work, session keys,
+// shares and the chunk steps that carry them, chunk transfer and announce frames, proof of work, session keys,
 // key exchange and handshake admission.  Many records per call, always on the MI355X; they throw
 // std::invalid_argument / std::runtime_error (not reference signatures).
 //
@@ -316,6 +316,146 @@ std::vector<OpenedChunk> chunk_frames_open(Keys32 session_table, std::span<const
             std::memcpy(&res[i].ttl_seconds, resv.data() + 4 * i, 4);
             res[i].plaintext.assign(pt.begin() + ooff[i], pt.begin() + ooff[i + 1]);
             res[i].stored.assign(ct.begin() + ooff[i], ct.begin() + ooff[i + 1]);
+        }
+        return res;
+    });
+}
+
+// ---- announce frames (enet_announce_frame_*_batch): every record brings its own manifest and
+// endpoint (the NULL-index form of the C ABI); the three field arenas share one offsets buffer
+SealedAnnounces announce_frames_seal(Keys32 session_table, std::span<const std::uint32_t> session,
+                                     std::span<const Nonce> nonces, std::span<const AnnounceFields> announces,
+                                     std::uint8_t difficulty, std::uint64_t max_attempts) {
+    const std::size_t n = announces.size(), K = session_table.size();
+    check_sizes("announce_frames_seal", n, {session.size(), nonces.size()});
+    check_count(n, "announce_frames_seal");
+    if (n == 0) return {};
+    check_sessions(session, K, "announce_frames_seal");
+    for (const AnnounceFields& a : announces)
+        if (a.peer_id != announces[0].peer_id)
+            throw std::invalid_argument("enet batch::announce_frames_seal: the announces of one call carry one peer_id");
+    // uri | endpoint | shard arenas and their offsets [3][n + 1]; the frame offsets
+    std::vector<std::uint8_t> uris, eps, shards;
+    std::vector<std::uint64_t> off(3 * (n + 1), 0), ooff(n + 1, 0);
+    for (std::size_t i = 0; i < n; ++i) {
+        const AnnounceFields& a = announces[i];
+        uris.insert(uris.end(), a.manifest_uri.begin(), a.manifest_uri.end());
+        eps.insert(eps.end(), a.endpoint.begin(), a.endpoint.end());
+        shards.insert(shards.end(), a.assigned_shards.begin(), a.assigned_shards.end());
+        off[i + 1] = uris.size();
+        off[n + 1 + i + 1] = eps.size();
+        off[2 * (n + 1) + i + 1] = shards.size();
+        const std::uint8_t v = a.version < 1 ? 1 : (a.version > 4 ? 4 : a.version);  // clamp_version
+        ooff[i + 1] = ooff[i] + 130 + a.manifest_uri.size() + a.endpoint.size() + a.assigned_shards.size() + (v == 4 ? 8 : 0);
+    }
+    // keys | chunk ids | work nonces | ttl | frame nonces | local id | versions
+    const std::size_t o_id = 32 * n, o_wn = 64 * n, o_ttl = 72 * n, o_non = 76 * n, o_pid = 88 * n, o_ver = 88 * n + 32;
+    std::vector<std::uint8_t> meta(89 * n + 32);
+    gather_session_keys(meta, session_table, session);
+    for (std::size_t i = 0; i < n; ++i) {
+        std::memcpy(meta.data() + o_id + 32 * i, announces[i].chunk_id.data(), 32);
+        std::memcpy(meta.data() + o_wn + 8 * i, &announces[i].work_nonce, 8);
+        std::memcpy(meta.data() + o_ttl + 4 * i, &announces[i].ttl_seconds, 4);
+        meta[o_ver + i] = announces[i].version;
+    }
+    std::memcpy(meta.data() + o_non, nonce_bytes(nonces), 12 * n);
+    std::memcpy(meta.data() + o_pid, announces[0].peer_id.data(), 32);
+    return staged([&](Staging& st) {
+        const std::size_t obytes = ooff[n];
+        auto* dout = st.room(S_OUT, obytes);
+        auto* dooff = st.up<uint64_t>(S_OUTOFF, ooff.data(), 8 * (n + 1));
+        auto* doff = st.up<uint64_t>(S_INOFF, off.data(), 8 * off.size());
+        // an arena may be empty (its vector then has no storage to copy from): room for one unread byte
+        auto arena = [&](Slot slot, const std::vector<std::uint8_t>& v) {
+            return v.empty() ? st.room(slot, 1) : st.up(slot, v.data(), v.size());
+        };
+        auto* duri = arena(S_IN, uris);
+        auto* dep = arena(S_AUX, eps);
+        auto* dsh = arena(S_TAGS, shards);
+        auto* dm = st.up(S_KEYS, meta.data(), meta.size());
+        auto* dst = st.room(S_OK, n);
+        enet_records r = records_of(n, nullptr, dooff, nullptr, dout, dm, dm + o_non);
+        enet_announce_fields f{};
+        f.manifests = f.endpoints = static_cast<std::uint32_t>(n);
+        f.chunk_ids = dm + o_id;
+        f.uris = duri;
+        f.uri_offsets = doff;
+        f.endpoint_bytes = dep;
+        f.endpoint_offsets = doff + (n + 1);
+        f.shards = dsh;
+        f.shard_offsets = doff + 2 * (n + 1);
+        f.peer_id = dm + o_pid;
+        f.ttl = reinterpret_cast<const uint32_t*>(dm + o_ttl);
+        f.versions = dm + o_ver;
+        auto* dwn = reinterpret_cast<uint64_t*>(dm + o_wn);
+        enet_check(enet_announce_frame_seal_batch(&r, nullptr, 0, nullptr, &f, difficulty, max_attempts, dwn, dst, st.s()),
+                   "announce_frame_seal");
+        std::vector<std::uint8_t> flat(obytes), status(n);
+        SealedAnnounces res;
+        res.work_nonce.resize(n);
+        st.d2h(flat.data(), dout, obytes);
+        st.d2h(res.work_nonce.data(), dwn, 8 * n);
+        st.d2h(status.data(), dst, n);
+        st.sync();
+        res.frames.resize(n);
+        res.status.resize(n);
+        for (std::size_t i = 0; i < n; ++i) {
+            res.status[i] = static_cast<AnnounceStatus>(status[i]);
+            if (res.status[i] == AnnounceStatus::Ok) res.frames[i].assign(flat.begin() + ooff[i], flat.begin() + ooff[i + 1]);
+        }
+        return res;
+    });
+}
+
+std::vector<OpenedAnnounce> announce_frames_open(Keys32 session_table, std::span<const std::uint32_t> session,
+                                                 Records frames, std::span<const PeerId> peers, std::uint8_t difficulty) {
+    const std::size_t n = frames.size(), K = session_table.size();
+    check_sizes("announce_frames_open", n, {session.size(), peers.size()});
+    check_count(n, "announce_frames_open");
+    if (n == 0) return {};
+    check_sessions(session, K, "announce_frames_open");
+    const Packed in = pack(frames);
+    const std::vector<std::uint64_t> ooff = offsets_of(frames, -48);
+    // session keys | peers
+    std::vector<std::uint8_t> meta(64 * n);
+    gather_session_keys(meta, session_table, session);
+    std::memcpy(meta.data() + 32 * n, peers.data()->data(), 32 * n);
+    return staged([&](Staging& st) {
+        const std::size_t obytes = ooff[n];
+        auto* din = st.up(S_IN, in.arena.data(), in.arena.size());
+        auto* dmsg = st.room(S_OUT, std::max<std::size_t>(obytes, 1));
+        auto* dioff = st.up<uint64_t>(S_INOFF, in.off.data(), 8 * (n + 1));
+        auto* dooff = st.up<uint64_t>(S_OUTOFF, ooff.data(), 8 * (n + 1));
+        auto* dm = st.up(S_KEYS, meta.data(), meta.size());
+        auto* dres = st.room(S_OK, 33 * n);  // info [n][8] uint32, then status [n]
+        const enet_records r = records_of(n, dioff, dooff, din, dmsg, dm, nullptr);
+        enet_check(enet_announce_frame_open_batch(&r, nullptr, 0, nullptr, dm + 32 * n, difficulty,
+                                                  reinterpret_cast<uint32_t*>(dres), dres + 32 * n, st.s()),
+                   "announce_frame_open");
+        std::vector<std::uint8_t> msg(obytes), resv(33 * n);
+        if (obytes) st.d2h(msg.data(), dmsg, obytes);
+        st.d2h(resv.data(), dres, resv.size());
+        st.sync();
+        std::vector<OpenedAnnounce> res(n);
+        for (std::size_t i = 0; i < n; ++i) {
+            res[i].status = static_cast<AnnounceStatus>(resv[32 * n + i]);
+            if (res[i].status != AnnounceStatus::Ok) {  // no field of a failed frame
+                res[i].fields.version = 0;
+                continue;
+            }
+            std::uint32_t info[8];
+            std::memcpy(info, resv.data() + 32 * i, 32);
+            const std::uint8_t* m = msg.data() + ooff[i];
+            AnnounceFields& a = res[i].fields;
+            a.version = static_cast<std::uint8_t>(info[0]);
+            a.ttl_seconds = info[1];
+            std::memcpy(a.chunk_id.data(), m + 18, 32);
+            std::memcpy(a.peer_id.data(), m + 50, 32);
+            const std::uint8_t* p = m + 82;
+            a.endpoint.assign(p, p + info[2]);
+            a.manifest_uri.assign(p + info[2], p + info[2] + info[3]);
+            a.assigned_shards.assign(p + info[2] + info[3], p + info[2] + info[3] + info[4]);
+            a.work_nonce = (static_cast<std::uint64_t>(info[6]) << 32) | info[5];
         }
         return res;
     });

@@ -834,14 +834,14 @@ int enet_wire_open_batch(const enet_records* r, uint8_t* macs, uint8_t* ok, void
     return frame_open(&q, kWireHeader, macs, ok, (hipStream_t)stream, "wire_open");
 }
 
-// chunk transfer frames: the session keys per record (session == NULL) or as a table
-static int chunk_frame_keys(enet::ChunkFrameParams& c, const uint32_t* session, uint32_t sessions,
+// chunk transfer and announce frames: the session keys per record (session == NULL) or as a table
+static int chunk_frame_keys(enet::DuplexParams& d, const uint32_t* session, uint32_t sessions,
                             const uint32_t* mid, const char* what) {
     if (!session) return ENET_OK;
     if (!mid || !aligned4(session) || !aligned4(mid) || sessions == 0) return fail(ENET_EINVAL, what);
-    c.d.session = session;
-    c.d.mid = mid;
-    c.d.n_sessions = sessions;
+    d.session = session;
+    d.mid = mid;
+    d.n_sessions = sessions;
     return ENET_OK;
 }
 
@@ -853,7 +853,7 @@ int enet_chunk_frame_seal_batch(const enet_records* r, const uint32_t* session, 
     if (!chunk_ids || !ttl || !aligned4(ttl)) return fail(ENET_EINVAL, "chunk_frame_seal: NULL chunk_ids, NULL/misaligned ttl");
     enet::ChunkFrameParams c{};
     c.d = duplex_params(r);
-    if (int e = chunk_frame_keys(c, session, sessions, mid, "chunk_frame_seal: NULL/misaligned session or mid, or no sessions")) return e;
+    if (int e = chunk_frame_keys(c.d, session, sessions, mid, "chunk_frame_seal: NULL/misaligned session or mid, or no sessions")) return e;
     c.chunk_ids = chunk_ids;
     c.ttl = ttl;
     c.versions = versions;
@@ -874,7 +874,7 @@ int enet_chunk_frame_open_batch(const enet_records* r, const uint32_t* session, 
     if (int e = check_records(&q, true)) return e;
     enet::ChunkFrameParams c{};
     c.d = duplex_params(&q);
-    if (int e = chunk_frame_keys(c, session, sessions, mid, "chunk_frame_open: NULL/misaligned session or mid, or no sessions")) return e;
+    if (int e = chunk_frame_keys(c.d, session, sessions, mid, "chunk_frame_open: NULL/misaligned session or mid, or no sessions")) return e;
     c.chunk_ids = chunk_ids;
     c.chunk_keys = chunk_keys;
     c.chunk_nonces = chunk_nonces;
@@ -883,6 +883,72 @@ int enet_chunk_frame_open_batch(const enet_records* r, const uint32_t* session, 
     c.ttl_out = ttl_out;
     c.status = status;
     return hip_status(enet::launch_chunk_frames(true, c, (hipStream_t)stream), "chunk_frame_open");
+}
+
+// announce frames: seal reads no input arena, so the descriptor's in / in_offsets stay unchecked
+int enet_announce_frame_seal_batch(const enet_records* r, const uint32_t* session, uint32_t sessions,
+                                   const uint32_t* mid, const enet_announce_fields* f, uint32_t difficulty,
+                                   uint64_t max_attempts, uint64_t* work_nonce, uint8_t* status, void* stream) {
+    if (!r) return fail(ENET_EINVAL, "records descriptor is NULL");
+    if (r->count == 0) return ENET_OK;
+    if (!f || !status || !work_nonce) return fail(ENET_EINVAL, "announce_frame_seal: NULL fields, status or work_nonce");
+    if (difficulty > 255) return fail(ENET_EINVAL, "announce_frame_seal: difficulty > 255");
+    if (reinterpret_cast<uintptr_t>(work_nonce) & 7u) return fail(ENET_EINVAL, "announce_frame_seal: work_nonce misaligned");
+    if (r->count > 0x7FFFFFFFu) return fail(ENET_EINVAL, "announce_frame_seal: too many records");
+    enet_records q = *r;
+    q.in = q.out;  // unread: the checks and the geometry see the output side twice
+    q.in_offsets = q.out_offsets;
+    if (int e = check_records(&q, true)) return e;
+    if (!f->chunk_ids || !f->uris || !f->uri_offsets || !f->endpoint_bytes || !f->endpoint_offsets || !f->shards ||
+        !f->shard_offsets || !f->peer_id || !f->ttl)
+        return fail(ENET_EINVAL, "announce_frame_seal: NULL field table");
+    if (!aligned4(f->ttl) || !aligned4(f->manifest) || !aligned4(f->endpoint) ||
+        ((reinterpret_cast<uintptr_t>(f->uri_offsets) | reinterpret_cast<uintptr_t>(f->endpoint_offsets) |
+          reinterpret_cast<uintptr_t>(f->shard_offsets)) & 7u))
+        return fail(ENET_EINVAL, "announce_frame_seal: misaligned ttl, index or offset table");
+    enet::AnnounceFrameParams c{};
+    c.d = duplex_params(&q);
+    c.d.in = nullptr;
+    if (int e = chunk_frame_keys(c.d, session, sessions, mid, "announce_frame_seal: NULL/misaligned session or mid, or no sessions")) return e;
+    c.manifests = f->manifests;
+    c.endpoints = f->endpoints;
+    c.chunk_ids = f->chunk_ids;
+    c.uris = f->uris;
+    c.uri_off = f->uri_offsets;
+    c.manifest = f->manifest;
+    c.endpoint_bytes = f->endpoint_bytes;
+    c.endpoint_off = f->endpoint_offsets;
+    c.endpoint = f->endpoint;
+    c.shards = f->shards;
+    c.shard_off = f->shard_offsets;
+    c.peer_id = f->peer_id;
+    c.ttl = f->ttl;
+    c.versions = f->versions;
+    c.difficulty = difficulty;
+    c.max_attempts = max_attempts;
+    c.work_nonce = work_nonce;
+    c.status = status;
+    return hip_status(enet::launch_announce_frames(false, c, (hipStream_t)stream), "announce_frame_seal");
+}
+
+int enet_announce_frame_open_batch(const enet_records* r, const uint32_t* session, uint32_t sessions,
+                                   const uint32_t* mid, const uint8_t* peer_ids, uint32_t difficulty, uint32_t* info,
+                                   uint8_t* status, void* stream) {
+    if (!r) return fail(ENET_EINVAL, "records descriptor is NULL");
+    if (r->count == 0) return ENET_OK;
+    if (!status || !info || !peer_ids) return fail(ENET_EINVAL, "announce_frame_open: NULL status, info or peer_ids");
+    if (!aligned4(info)) return fail(ENET_EINVAL, "announce_frame_open: info misaligned");
+    if (difficulty > 255) return fail(ENET_EINVAL, "announce_frame_open: difficulty > 255");
+    const enet_records q = with_frame_nonce(r);
+    if (int e = check_records(&q, true)) return e;
+    enet::AnnounceFrameParams c{};
+    c.d = duplex_params(&q);
+    if (int e = chunk_frame_keys(c.d, session, sessions, mid, "announce_frame_open: NULL/misaligned session or mid, or no sessions")) return e;
+    c.peer_ids = peer_ids;
+    c.difficulty = difficulty;
+    c.info = info;
+    c.status = status;
+    return hip_status(enet::launch_announce_frames(true, c, (hipStream_t)stream), "announce_frame_open");
 }
 
 int enet_pow_search_batch(uint32_t n, const uint8_t* prefixes, const uint64_t* prefix_offsets,
@@ -894,10 +960,7 @@ int enet_pow_search_batch(uint32_t n, const uint8_t* prefixes, const uint64_t* p
     if (schedule != ENET_POW_NODE && schedule != ENET_POW_STORE)
         return fail(ENET_EINVAL, "pow_search: schedule must be ENET_POW_NODE or ENET_POW_STORE");
     if (n > 0x7FFFFFFFu) return fail(ENET_EINVAL, "pow_search: too many jobs");
-    // one workgroup per job: enough waves per job that the grid holds ~4 waves per SIMD
-    // (1024 SIMDs), at most 16 (1024 threads), never more lanes than attempts
-    uint32_t waves = 1;
-    while (waves < 16 && (uint64_t)n * waves < 4096 && 64ull * waves < max_attempts) waves <<= 1;
+    const uint32_t waves = enet::pow_search_waves(n, max_attempts);  // one workgroup per job
     enet::PowParams p{};
     p.n = n;
     p.prefixes = prefixes;

@@ -153,6 +153,39 @@ struct ChunkFrameParams {
 };
 hipError_t launch_chunk_frames(bool open, const ChunkFrameParams& p, hipStream_t s);
 
+// Announce frames (announce_frames.hip): an `Announce` message (Message.cpp:215-235) inside a wire
+// frame.  Seal gathers the message from the manifest / endpoint / shard arenas and, at difficulty
+// > 0, searches the announce proof of work first (compute_announce_pow, Node.cpp:212-230); open
+// undoes the frame and runs handle_announce's admission checks (Node.cpp:2332-2357, :1144-1151).
+// d carries the output arena and offsets, order, the session keys and, for seal, the frame
+// nonces; seal reads no input arena (d.in_off = d.out_off, d.in unused).
+constexpr uint32_t kAnnounceFixed = 82;  // version, type, BE32 ttl / E / U / A, chunk_id, peer_id
+struct AnnounceFrameParams {
+    DuplexParams d;
+    // seal: the enet_announce_fields of the C ABI
+    uint32_t manifests, endpoints;
+    const uint8_t *chunk_ids, *uris, *endpoint_bytes, *shards, *peer_id, *versions;
+    const uint64_t *uri_off, *endpoint_off, *shard_off;
+    const uint32_t *manifest, *endpoint, *ttl;
+    uint64_t max_attempts;
+    uint64_t* work_nonce;      // [n]: found by the search, or the caller's when max_attempts == 0
+    int searched;              // the seal kernel: the search launch ran and left status / work_nonce
+    // open
+    const uint8_t* peer_ids;   // [n][32]: the sessions' peers
+    uint32_t* info;            // [n][8]: version, ttl, E, U, A, nonce low, nonce high, 0
+    uint32_t difficulty;
+    uint8_t* status;           // ENET_AF_* of enet_crypto.h
+};
+hipError_t launch_announce_frames(bool open, const AnnounceFrameParams& p, hipStream_t s);
+
+// waves per searching workgroup: enough that a grid of n jobs holds ~4 waves per SIMD (1024
+// SIMDs), at most 16 (1024 threads), never more lanes than attempts
+inline uint32_t pow_search_waves(uint32_t n, uint64_t max_attempts) {
+    uint32_t waves = 1;
+    while (waves < 16 && (uint64_t)n * waves < 4096 && 64ull * waves < max_attempts) waves <<= 1;
+    return waves;
+}
+
 // Proof-of-work search / check (pow.hip): SHA-256(prefix_i || BE64(candidate)).
 struct PowParams {
     uint32_t n;

@@ -269,6 +269,95 @@ ENET_API int enet_pow_check_batch(uint32_t n, const uint8_t* prefixes,
                                   const uint64_t* prefix_offsets, const uint64_t* nonces,
                                   const uint8_t* difficulty, uint8_t* ok, void* stream);
 
+/* ---- announce frames: batched PoW + seal, and one-pass admission
+ * The gossip of a manifest is an `Announce` message per assigned peer and endpoint
+ * (Node::broadcast_manifest -> deliver_manifest, src/core/Node.cpp:2512-2661): a proof-of-work
+ * search (compute_announce_pow, :212-230), encode + encode_signed (src/protocol/Message.cpp:215-235,
+ * 305-311) and the session frame.  With E, U, A the lengths of endpoint, manifest URI and assigned
+ * shards and v the version after clamp_version (1..4):
+ *   m_i     = v || 0x01 || BE32(ttl) || BE32(E) || BE32(U) || BE32(A) || chunk_id(32) || peer_id(32)
+ *             || endpoint || uri || shards || [BE64(work_nonce) only when v == 4]
+ *   frame_i = nonce_i(12) || BE32(|m_i| + 32) || ChaCha20_{Ks_i, nonce_i, 0}(m_i || HMAC_{Ks_i}(m_i))
+ *   pow_i   = SHA-256(BE64(32) || chunk_id || BE64(32) || peer_id || BE64(E) || endpoint || BE64(U)
+ *             || uri || BE64(A) || shards || BE64(ttl) || BE64(work_nonce))        (Node.cpp:155-173)
+ * The receiver (handle_transport_message -> decode_signed -> handle_announce, Node.cpp:2160-2179,
+ * 2332-2357) opens the frame, checks the HMAC, parses m, then checks peer_id == sender, a non-empty
+ * URI and announce_pow_valid (:193-198, :1144-1151).  Two quirks of the reference are kept: encode
+ * writes the nonce only for v == 4 but decode expects it for v >= 3 (Message.cpp:221, 284), so a
+ * v3 announce made by encode never decodes; v1 / v2 carry no nonce and fail the PoW check whenever
+ * difficulty > 0.
+ * Session keys for both calls: as in enet_chunk_frame_*_batch (session != NULL: r->keys is the
+ * table, mid its midstates; session == NULL: per-record keys).  count, out / out_offsets, order
+ * and the hints keep their enet_records meaning.  All arrays are device pointers.
+ * seal: r->in / r->in_offsets are ignored; r->nonces = the frame nonces; out_i = frame_i,
+ *       out_offsets must give |out_i| = |m_i| + 48.  The fields come through index tables because
+ *       one manifest goes to many peers: record i takes chunk id and URI of manifest
+ *       f->manifest[i], the endpoint f->endpoint[i] (NULL tables: i), its own shard list and ttl;
+ *       f->peer_id is the local id; ttl is uint32 because that is all the wire carries (the
+ *       receiver's digest sees the truncated value).  Neither m nor the PoW prefix is written to
+ *       device memory.  At most two launches, no synchronisation, no allocation, no scratch:
+ *       the search (one workgroup per record, first-found order, ENET_POW_NODE schedule) runs only
+ *       when difficulty > 0 and max_attempts > 0, and only for v == 4 records; v < 4 records are
+ *       sealed as encode writes them, without a nonce (work_nonce[i] = 0) -- deliver_manifest's
+ *       "difficulty > 0 needs v >= 3" guard (Node.cpp:2639) stays with the caller.  difficulty ==
+ *       0: nonce 0, as compute_announce_pow.  max_attempts == 0: work_nonce[] is INPUT (a search
+ *       done earlier), nothing is searched, whatever the difficulty.  work_nonce [n] (8-byte
+ *       aligned) otherwise receives the nonces.  status [n]:
+ *         0 ENET_AF_OK
+ *         1 ENET_AF_FRAME   the output length does not fit, or a session / manifest / endpoint
+ *                           index is outside its table (or a field's offsets decrease)
+ *         5 ENET_AF_POW     no nonce within max_attempts
+ *       On a non-zero status the record's whole output slot is zero and work_nonce[i] = 0.
+ * open: in_i = a received frame (the nonce is read from it; r->nonces may be NULL); peer_ids
+ *       [n][32] = the peer of each frame's session; out_i = m_i, out_offsets must give |in_i| - 48
+ *       (0 for shorter frames); info [n][8] uint32 (4-byte aligned) = {v, ttl, E, U, A, nonce low,
+ *       nonce high, 0}: the fields lie in out_i at 82, 82 + E and 82 + E + U.  status [n] = the
+ *       first check that failed, in the reference's order:
+ *         0 ENET_AF_OK
+ *         1 ENET_AF_FRAME        what gives enet_wire_open_batch ok = 0: frame < 48 bytes, length
+ *                                field != body length, HMAC mismatch, session index outside the
+ *                                table, or the output length does not fit
+ *         2 ENET_AF_HEADER       version outside 1..4, type != 0x01, or |m| != 82 + E + U + A
+ *                                (+ 8 if v >= 3), summed in 64 bits (parse_announce_payload,
+ *                                Message.cpp:75-121)
+ *         3 ENET_AF_SENDER       the message's peer_id != peer_ids[i] (Node.cpp:2341)
+ *         4 ENET_AF_NO_MANIFEST  U == 0 (:2347)
+ *         5 ENET_AF_POW          difficulty > 0 and (v < 3 or leading zero bits of pow < difficulty)
+ *       On any non-zero status the record's out range and info[i] are zero when the call returns.
+ *       Records `order` does not name are untouched.  One deliberate difference, as for Chunk
+ *       frames: decode accepts bytes after the payload (remaining < expected_size is its only
+ *       length check), this call reports ENET_AF_HEADER and the caller falls back to
+ *       enet_wire_open_batch_sessions.
+ *       One launch; every frame byte is read from HBM once (cipher, mac and pow lane per record).
+ * ENET_EINVAL, with nothing launched: NULL r, f, status, work_nonce / info, peer_ids or a NULL
+ * required table of f; difficulty > 255; misaligned info / work_nonce / ttl / index tables.
+ * count == 0 is a no-op whatever else is passed. */
+enum { ENET_AF_OK = 0, ENET_AF_FRAME = 1, ENET_AF_HEADER = 2, ENET_AF_SENDER = 3, ENET_AF_NO_MANIFEST = 4,
+       ENET_AF_POW = 5 };
+typedef struct enet_announce_fields {
+    uint32_t manifests;               /* M */
+    const uint8_t* chunk_ids;         /* [M][32] */
+    const uint8_t* uris;              /* URI arena */
+    const uint64_t* uri_offsets;      /* [M+1] */
+    const uint32_t* manifest;         /* [n] index into the M manifests, NULL: i */
+    uint32_t endpoints;               /* Ep */
+    const uint8_t* endpoint_bytes;    /* endpoint arena */
+    const uint64_t* endpoint_offsets; /* [Ep+1] */
+    const uint32_t* endpoint;         /* [n] index into the Ep endpoints, NULL: i */
+    const uint8_t* shards;            /* assigned-shard arena, per record */
+    const uint64_t* shard_offsets;    /* [n+1] */
+    const uint8_t* peer_id;           /* [32] the local id */
+    const uint32_t* ttl;              /* [n] seconds */
+    const uint8_t* versions;          /* [n], NULL = 4, clamped to 1..4 */
+} enet_announce_fields;
+ENET_API int enet_announce_frame_seal_batch(const enet_records* r, const uint32_t* session, uint32_t sessions,
+                                            const uint32_t* mid, const enet_announce_fields* f,
+                                            uint32_t difficulty, uint64_t max_attempts, uint64_t* work_nonce,
+                                            uint8_t* status, void* stream);
+ENET_API int enet_announce_frame_open_batch(const enet_records* r, const uint32_t* session, uint32_t sessions,
+                                            const uint32_t* mid, const uint8_t* peer_ids, uint32_t difficulty,
+                                            uint32_t* info, uint8_t* status, void* stream);
+
 /* ---- session key derivation
  * network::KeyManager::derive_key (src/network/KeyManager.cpp:74-92) for n sessions:
  * keys_out[i] = HMAC-SHA256(secrets[i], BE64(counters[i]) || BE64(ticks[i])), ticks = the

@@ -10,6 +10,7 @@
 #include <future>
 #include <optional>
 #include <span>
+#include <string>
 #include <string_view>
 #include <vector>
 
@@ -209,6 +210,54 @@ ENET_CXX_API std::vector<OpenedChunk> chunk_frames_open(
     std::span<const Key> chunk_keys, std::span<const Nonce> chunk_nonces,
     std::span<const std::array<std::uint8_t, 32>> chunk_hashes);
 
+// Announce frames (enet_announce_frame_*_batch): the gossip of a manifest, batched.
+// announce_frames_seal is Node::deliver_manifest's crypto (Node.cpp:2512-2661) for many peers at
+// once: the announce proof of work (compute_announce_pow, :212-230; at most max_attempts
+// candidates, searched only for version-4 records and difficulty > 0; max_attempts == 0: the
+// announces' own work_nonce is used), then frame i = the wire frame, under
+// session_table[session[i]] and nonces[i], of the signed Announce message encode writes
+// (Message.cpp:215-235: the version clamped to 1..4, the nonce only for version 4).  The caller
+// keeps deliver_manifest's guard (difficulty > 0 needs version >= 3, Node.cpp:2639).  Every
+// announce of one call carries the same peer_id, the local id.  A record without a nonce within
+// max_attempts comes back with status Pow, an empty frame and nonce 0.
+// announce_frames_open is the receive side (decode_signed -> handle_announce, Node.cpp:2332-2357):
+// the frame is opened, the message parsed (decode expects the nonce for version >= 3, so a
+// version-3 announce made by encode reports Header), peer_id compared with peers[i], an empty URI
+// refused and the proof of work checked at `difficulty` (0: none asked; version < 3 fails any
+// other, :1144-1151).  status = the first check that failed, in that order; a failed frame comes
+// back with empty fields.  An Announce with bytes after its payload reports Header (decode would
+// accept it; encode never writes one).  ttl is 32 bits wide: all the wire carries.  Throws
+// std::invalid_argument for a size mismatch, a session index outside the table or differing
+// peer_ids in one seal.
+enum class AnnounceStatus : std::uint8_t { Ok = 0, Frame = 1, Header = 2, Sender = 3, NoManifest = 4, Pow = 5 };
+struct AnnounceFields {
+    ChunkId chunk_id{};
+    PeerId peer_id{};
+    std::string endpoint;
+    std::uint32_t ttl_seconds = 0;
+    std::string manifest_uri;
+    std::vector<std::uint8_t> assigned_shards;
+    std::uint8_t version = 4;
+    std::uint64_t work_nonce = 0;
+};
+struct SealedAnnounces {
+    std::vector<std::vector<std::uint8_t>> frames;
+    std::vector<std::uint64_t> work_nonce;
+    std::vector<AnnounceStatus> status;
+};
+struct OpenedAnnounce {
+    AnnounceStatus status = AnnounceStatus::Frame;
+    AnnounceFields fields;
+};
+inline constexpr std::uint64_t kNodePowAttempts = 500'000;  // kMaxAnnouncePowAttempts, Node.cpp:40
+ENET_CXX_API SealedAnnounces announce_frames_seal(
+    std::span<const std::array<std::uint8_t, 32>> session_table, std::span<const std::uint32_t> session,
+    std::span<const Nonce> nonces, std::span<const AnnounceFields> announces, std::uint8_t difficulty,
+    std::uint64_t max_attempts = kNodePowAttempts);
+ENET_CXX_API std::vector<OpenedAnnounce> announce_frames_open(
+    std::span<const std::array<std::uint8_t, 32>> session_table, std::span<const std::uint32_t> session,
+    std::span<const std::span<const std::uint8_t>> frames, std::span<const PeerId> peers, std::uint8_t difficulty);
+
 // Cross-session frame queues.  SessionManager runs one detached reader
 // thread per session (SessionManager.cpp:332-333, receive_loop :703-854) and sends from whatever
 // thread calls Node::send_secure (:337-388), one ChaCha20 + HMAC per frame on that thread.  Here
@@ -391,7 +440,7 @@ ENET_CXX_API std::vector<std::uint8_t> handshake_pow_prefix(const PeerId& initia
 // attempt order and 500'000-attempt cap (Node.cpp:40,43), same nonce.  difficulty 0 -> nonce 0,
 // true.  Not found -> false and nonce_out untouched.  One device search replaces up to 500'000
 // host Sha256 constructions; a maintainer makes the Node.cpp helpers forward here.
-inline constexpr std::uint64_t kNodePowAttempts = 500'000;
+// (kNodePowAttempts: above, beside announce_frames_seal.)
 ENET_CXX_API bool compute_announce_pow(const ChunkId& chunk_id, const PeerId& peer_id, std::string_view endpoint,
                                        std::string_view manifest_uri,
                                        std::span<const std::uint8_t> assigned_shards, std::int64_t ttl_seconds,
