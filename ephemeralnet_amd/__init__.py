@@ -23,6 +23,10 @@ Operations mirror the reference src/crypto API, batched (ShardianLabs/EphemeralN
                   src/core/Node.cpp:1254-1297, 1615-1677, src/protocol/Message.cpp:204-246
   announce_frame_seal/open compute_announce_pow + encode_signed + frame, and handle_announce's admission
                   src/core/Node.cpp:155-230, 2332-2357, 2512-2661, src/protocol/Message.cpp:215-235
+  control_frame_seal/open Request / Acknowledge messages as session frames, and back
+                  src/core/Node.cpp:532-550, 930-949, 1748-1756, 2305-2317, src/protocol/Message.cpp:236-252
+  frame_classify receive-side triage of mixed frames into per-type `order` lists
+                  src/network/SessionManager.cpp:760-822, src/core/Node.cpp:2160-2179
 """
 from __future__ import annotations
 
@@ -82,6 +86,7 @@ EXPORTS = [
     "enet_handshake_accept_batch", "enet_session_rotate_batch", "enet_key_exchange_batch",
     "enet_chunk_frame_seal_batch", "enet_chunk_frame_open_batch",
     "enet_announce_frame_seal_batch", "enet_announce_frame_open_batch",
+    "enet_control_frame_seal_batch", "enet_control_frame_open_batch", "enet_frame_classify_batch",
 ]
 
 # status of chunk_frame_open (enet_crypto.h): the first failed check
@@ -90,6 +95,11 @@ ENET_CF_OK, ENET_CF_FRAME, ENET_CF_HEADER, ENET_CF_CHUNK_ID, ENET_CF_HASH = 0, 1
 # status of announce_frame_seal / announce_frame_open (enet_crypto.h): the first failed check
 ENET_AF_OK, ENET_AF_FRAME, ENET_AF_HEADER, ENET_AF_SENDER, ENET_AF_NO_MANIFEST, ENET_AF_POW = 0, 1, 2, 3, 4, 5
 NODE_POW_ATTEMPTS = 500_000  # kMaxAnnouncePowAttempts, src/core/Node.cpp:40
+
+# control_frame_seal kinds, control_frame_seal / control_frame_open status, frame_classify kinds (enet_crypto.h)
+ENET_CTL_REQUEST, ENET_CTL_ACK = 2, 4
+ENET_CT_OK, ENET_CT_FRAME, ENET_CT_HEADER = 0, 1, 2
+ENET_FK_BAD, ENET_FK_ANNOUNCE, ENET_FK_REQUEST, ENET_FK_CHUNK, ENET_FK_ACK, ENET_FK_OTHER = 0, 1, 2, 3, 4, 5
 
 
 class _AnnounceFields(C.Structure):
@@ -266,6 +276,9 @@ def lib() -> C.CDLL:
         L.enet_chunk_frame_open_batch.argtypes = [rp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.enet_announce_frame_seal_batch.argtypes = [rp, vp, u32, vp, C.POINTER(_AnnounceFields), u32, u64, vp, vp, vp]
         L.enet_announce_frame_open_batch.argtypes = [rp, vp, u32, vp, vp, u32, vp, vp, vp]
+        L.enet_control_frame_seal_batch.argtypes = [rp, vp, u32, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp]
+        L.enet_control_frame_open_batch.argtypes = [rp, vp, u32, vp, vp, vp, vp, vp, vp, vp]
+        L.enet_frame_classify_batch.argtypes = [rp, vp, u32, vp, vp, vp, vp]
         for name in EXPORTS:
             getattr(L, name)
         _lib = L
@@ -569,6 +582,49 @@ def announce_frame_open(b: Batch, out, out_offsets, peer_ids, difficulty: int, i
     _check(lib().enet_announce_frame_open_batch(C.byref(r), _ptr(session), sessions, _ptr(mid), _ptr(peer_ids),
                                                 int(difficulty), _ptr(info), _ptr(status), _stream(stream)),
            "enet_announce_frame_open_batch")
+
+
+def control_frame_seal(b: Batch, out, out_offsets, kinds, chunk_ids, peer_id, status, accepted=None, accept_zero=False,
+                       versions=None, session=None, sessions=0, mid=None, stream=None) -> None:
+    """Request / Acknowledge send (Node::request_chunk, handle_chunk's ack, send_negative_ack): out_i =
+    the 114-byte wire frame of version || 0x02 || chunk_ids[i] || peer_id (kinds[i] = ENET_CTL_REQUEST)
+    or the 115-byte frame of version || 0x04 || accepted || chunk_ids[i] || peer_id (ENET_CTL_ACK).
+    b.arena / b.offsets are not read (b.offsets only gives the batch size); b.nonces = the frame
+    nonces, b.keys the session keys (per record, or the table with `session` int32 [n] / `sessions` /
+    `mid`).  kinds uint8 [n], chunk_ids uint8 [n,32], peer_id uint8 [32] (the local id), versions uint8
+    [n] (None = 4; clamped to 1..4), accepted uint8 [n] (None = 0); accept_zero: the wire byte is
+    accepted[i] == 0, so chunk_frame_open's status can be passed as it is.  status uint8 [n] =
+    ENET_CT_OK / ENET_CT_FRAME / ENET_CT_HEADER; a failed record's slot is zero."""
+    r = b.records(out, out_offsets)
+    _check(lib().enet_control_frame_seal_batch(C.byref(r), _ptr(session), sessions, _ptr(mid), _ptr(kinds),
+                                               _ptr(chunk_ids), _ptr(peer_id), _ptr(accepted), int(bool(accept_zero)),
+                                               _ptr(versions), _ptr(status), _stream(stream)),
+           "enet_control_frame_seal_batch")
+
+
+def control_frame_open(b: Batch, chunk_ids_out, info, status, peer_ids_out=None, sender_ids=None, session=None,
+                       sessions=0, mid=None, stream=None) -> None:
+    """Request / Acknowledge receive (decode_signed -> decode): b.arena holds received wire frames
+    (nonces come from the frames; b.nonces may be None), b.keys the session keys as in
+    control_frame_seal.  chunk_ids_out / peer_ids_out uint8 [n,32], info uint8 [n,4] = version, type,
+    accepted, sender_match (the message's requester / peer_id equals sender_ids[i], uint8 [n,32];
+    reported, not enforced), status uint8 [n] = ENET_CT_*: the first failed check; a failed record's
+    ids and info are zero."""
+    r = b.records(None, None)
+    _check(lib().enet_control_frame_open_batch(C.byref(r), _ptr(session), sessions, _ptr(mid), _ptr(sender_ids),
+                                               _ptr(chunk_ids_out), _ptr(peer_ids_out), _ptr(info), _ptr(status),
+                                               _stream(stream)), "enet_control_frame_open_batch")
+
+
+def frame_classify(b: Batch, kind, lists, counts, session=None, sessions=0, stream=None) -> None:
+    """Receive-side triage: b.arena holds received wire frames of unknown type; kind uint8 [n] =
+    ENET_FK_* from one keystream block per frame (nothing is authenticated), lists int32 [5,n] /
+    counts int32 [5]: row k - 1 = the indices of the frames of kind k, to be passed as `order` /
+    `count` to announce_frame_open, control_frame_open (rows 2 and 4), chunk_frame_open and, for row
+    5, wire_open_sessions.  counts is zeroed by the call on the stream."""
+    r = b.records(None, None)
+    _check(lib().enet_frame_classify_batch(C.byref(r), _ptr(session), sessions, _ptr(kind), _ptr(lists),
+                                           _ptr(counts), _stream(stream)), "enet_frame_classify_batch")
 
 
 def pow_search(prefixes, offsets, difficulty, schedule: int, max_attempts: int, nonces, found,

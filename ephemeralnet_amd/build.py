@@ -25,7 +25,7 @@ OBJ = os.path.join(PKG, "build")
 LIB_TOOLS = os.path.join(PKG, "libenet_crypto_tools.so")
 OBJ_TOOLS = os.path.join(PKG, "build_tools")
 SOURCES = ["records.hip", "segments.hip", "stream.hip", "sha.hip", "pow.hip", "duplex.hip", "duplex_split.hip",
-           "chunk_frames.hip", "announce_frames.hip",
+           "chunk_frames.hip", "announce_frames.hip", "control_frames.hip",
            "shamir.hip", "shamir_host.cpp", "handshake.hip",
            "capi.cpp", "long_records.cpp", "chunk_hybrid.cpp", "staging.cpp", "scalar_api.cpp", "batch_records.cpp",
            "batch_staged.cpp", "pipeline.cpp", "host_engine.cpp",

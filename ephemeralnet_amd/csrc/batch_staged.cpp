@@ -1,6 +1,7 @@
 // batch_staged.cpp -- the crypto::batch and security::batch calls (Batch.hpp, StoreProof.hpp) that
 // drive the C ABI themselves over the calling thread's staging (staging.hpp): SHA-256, Shamir key
-// shares and the chunk steps that carry them, chunk transfer and announce frames, proof of work, session keys,
+// shares and the chunk steps that carry them, chunk transfer, announce and Request / Acknowledge frames,
+// frame triage, proof of work, session keys,
 // key exchange and handshake admission.  Many records per call, always on the MI355X; they throw
 // std::invalid_argument / std::runtime_error (not reference signatures).
 //
@@ -457,6 +458,119 @@ std::vector<OpenedAnnounce> announce_frames_open(Keys32 session_table, std::span
             a.assigned_shards.assign(p + info[2] + info[3], p + info[2] + info[3] + info[4]);
             a.work_nonce = (static_cast<std::uint64_t>(info[6]) << 32) | info[5];
         }
+        return res;
+    });
+}
+
+// ---- Request / Acknowledge frames and triage (enet_control_frame_*_batch, enet_frame_classify_batch)
+SealedControls control_frames_seal(Keys32 session_table, std::span<const std::uint32_t> session,
+                                   std::span<const Nonce> nonces, std::span<const ControlFields> controls,
+                                   const PeerId& local_id) {
+    const std::size_t n = controls.size(), K = session_table.size();
+    check_sizes("control_frames_seal", n, {session.size(), nonces.size()});
+    check_count(n, "control_frames_seal");
+    if (n == 0) return {};
+    check_sessions(session, K, "control_frames_seal");
+    std::vector<std::uint64_t> ooff(n + 1, 0);
+    for (std::size_t i = 0; i < n; ++i) ooff[i + 1] = ooff[i] + (controls[i].kind == ControlKind::Request ? 114 : 115);
+    // keys | chunk ids | frame nonces | local id | kinds | accepted | versions
+    const std::size_t o_id = 32 * n, o_non = 64 * n, o_pid = 76 * n, o_kind = 76 * n + 32, o_acc = o_kind + n, o_ver = o_acc + n;
+    std::vector<std::uint8_t> meta(79 * n + 32);
+    gather_session_keys(meta, session_table, session);
+    for (std::size_t i = 0; i < n; ++i) {
+        std::memcpy(meta.data() + o_id + 32 * i, controls[i].chunk_id.data(), 32);
+        meta[o_kind + i] = static_cast<std::uint8_t>(controls[i].kind);
+        meta[o_acc + i] = controls[i].accepted ? 1 : 0;
+        meta[o_ver + i] = controls[i].version;
+    }
+    std::memcpy(meta.data() + o_non, nonce_bytes(nonces), 12 * n);
+    std::memcpy(meta.data() + o_pid, local_id.data(), 32);
+    return staged([&](Staging& st) {
+        const std::size_t obytes = ooff[n];
+        auto* dout = st.room(S_OUT, obytes);
+        auto* dooff = st.up<uint64_t>(S_OUTOFF, ooff.data(), 8 * (n + 1));
+        auto* dm = st.up(S_KEYS, meta.data(), meta.size());
+        auto* dst = st.room(S_OK, n);
+        const enet_records r = records_of(n, nullptr, dooff, nullptr, dout, dm, dm + o_non);
+        enet_check(enet_control_frame_seal_batch(&r, nullptr, 0, nullptr, dm + o_kind, dm + o_id, dm + o_pid, dm + o_acc, 0,
+                                                 dm + o_ver, dst, st.s()),
+                   "control_frame_seal");
+        std::vector<std::uint8_t> flat(obytes), status(n);
+        st.d2h(flat.data(), dout, obytes);
+        st.d2h(status.data(), dst, n);
+        st.sync();
+        SealedControls res;
+        res.frames.resize(n);
+        res.status.resize(n);
+        for (std::size_t i = 0; i < n; ++i) {
+            res.status[i] = static_cast<ControlStatus>(status[i]);
+            if (res.status[i] == ControlStatus::Ok) res.frames[i].assign(flat.begin() + ooff[i], flat.begin() + ooff[i + 1]);
+        }
+        return res;
+    });
+}
+
+std::vector<OpenedControl> control_frames_open(Keys32 session_table, std::span<const std::uint32_t> session,
+                                               Records frames, std::span<const PeerId> senders) {
+    const std::size_t n = frames.size(), K = session_table.size();
+    check_sizes("control_frames_open", n, {session.size(), optional_size(senders, n)});
+    check_count(n, "control_frames_open");
+    if (n == 0) return {};
+    check_sessions(session, K, "control_frames_open");
+    const Packed in = pack(frames);
+    // session keys | senders
+    std::vector<std::uint8_t> meta(64 * n);
+    gather_session_keys(meta, session_table, session);
+    if (!senders.empty()) std::memcpy(meta.data() + 32 * n, senders.data()->data(), 32 * n);
+    return staged([&](Staging& st) {
+        auto* din = st.up(S_IN, in.arena.data(), in.arena.size());
+        auto* dioff = st.up<uint64_t>(S_INOFF, in.off.data(), 8 * (n + 1));
+        auto* dm = st.up(S_KEYS, meta.data(), meta.size());
+        auto* dres = st.room(S_OK, 69 * n);  // chunk ids [n][32], peer ids [n][32], info [n][4], status [n]
+        const enet_records r = records_of(n, dioff, nullptr, din, nullptr, dm, nullptr);
+        enet_check(enet_control_frame_open_batch(&r, nullptr, 0, nullptr, senders.empty() ? nullptr : dm + 32 * n, dres,
+                                                 dres + 32 * n, dres + 64 * n, dres + 68 * n, st.s()),
+                   "control_frame_open");
+        std::vector<std::uint8_t> resv(69 * n);
+        st.d2h(resv.data(), dres, resv.size());
+        st.sync();
+        std::vector<OpenedControl> res(n);
+        for (std::size_t i = 0; i < n; ++i) {
+            OpenedControl& c = res[i];
+            const std::uint8_t* info = resv.data() + 64 * n + 4 * i;
+            c.status = static_cast<ControlStatus>(resv[68 * n + i]);
+            c.version = info[0];
+            c.type = info[1];
+            c.accepted = info[2] != 0;
+            c.sender_match = info[3] != 0;
+            std::memcpy(c.chunk_id.data(), resv.data() + 32 * i, 32);
+            std::memcpy(c.peer_id.data(), resv.data() + 32 * n + 32 * i, 32);
+        }
+        return res;
+    });
+}
+
+std::vector<FrameKind> classify_frames(Keys32 session_table, std::span<const std::uint32_t> session, Records frames) {
+    const std::size_t n = frames.size(), K = session_table.size();
+    check_sizes("classify_frames", n, {session.size()});
+    check_count(n, "classify_frames");
+    if (n == 0) return {};
+    check_sessions(session, K, "classify_frames");
+    const Packed in = pack(frames);
+    std::vector<std::uint8_t> keys(32 * n);
+    gather_session_keys(keys, session_table, session);
+    return staged([&](Staging& st) {
+        auto* din = st.up(S_IN, in.arena.data(), in.arena.size());
+        auto* dioff = st.up<uint64_t>(S_INOFF, in.off.data(), 8 * (n + 1));
+        auto* dk = st.up(S_KEYS, keys.data(), keys.size());
+        auto* dlists = reinterpret_cast<uint32_t*>(st.room(S_OUT, 20 * n + 20));  // lists [5][n], counts [5]
+        auto* dkind = st.room(S_OK, n);
+        const enet_records r = records_of(n, dioff, nullptr, din, nullptr, dk, nullptr);
+        enet_check(enet_frame_classify_batch(&r, nullptr, 0, dkind, dlists, dlists + 5 * n, st.s()), "frame_classify");
+        std::vector<FrameKind> res(n);
+        static_assert(sizeof(FrameKind) == 1);
+        st.d2h(res.data(), dkind, n);
+        st.sync();
         return res;
     });
 }

@@ -951,6 +951,86 @@ int enet_announce_frame_open_batch(const enet_records* r, const uint32_t* sessio
     return hip_status(enet::launch_announce_frames(true, c, (hipStream_t)stream), "announce_frame_open");
 }
 
+// Request / Acknowledge frames: seal reads no input arena, open and classify write no output arena,
+// so the descriptor's unused side stays unchecked (the geometry sees the used side twice)
+int enet_control_frame_seal_batch(const enet_records* r, const uint32_t* session, uint32_t sessions,
+                                  const uint32_t* mid, const uint8_t* kinds, const uint8_t* chunk_ids,
+                                  const uint8_t* peer_id, const uint8_t* accepted, int accept_zero,
+                                  const uint8_t* versions, uint8_t* status, void* stream) {
+    if (!r) return fail(ENET_EINVAL, "records descriptor is NULL");
+    if (r->count == 0) return ENET_OK;
+    if (!kinds || !chunk_ids || !peer_id || !status) return fail(ENET_EINVAL, "control_frame_seal: NULL kinds, chunk_ids, peer_id or status");
+    if (!aligned4(chunk_ids) || !aligned4(peer_id)) return fail(ENET_EINVAL, "control_frame_seal: chunk_ids or peer_id misaligned");
+    enet_records q = *r;
+    q.in = q.out;
+    q.in_offsets = q.out_offsets;
+    if (int e = check_records(&q, true)) return e;
+    enet::ControlFrameParams c{};
+    c.d = duplex_params(&q);
+    c.d.in = nullptr;
+    if (int e = chunk_frame_keys(c.d, session, sessions, mid, "control_frame_seal: NULL/misaligned session or mid, or no sessions")) return e;
+    c.kinds = kinds;
+    c.chunk_ids = chunk_ids;
+    c.peer_id = peer_id;
+    c.accepted = accepted;
+    c.accept_zero = accept_zero;
+    c.versions = versions;
+    c.status = status;
+    return hip_status(enet::launch_control_frames(enet::CT_SEAL, c, (hipStream_t)stream), "control_frame_seal");
+}
+
+// the received side of a descriptor: frames in, nothing out (the nonce comes from the frame)
+static enet_records received_frames(const enet_records* r) {
+    enet_records q = with_frame_nonce(r);
+    q.out = const_cast<uint8_t*>(q.in);  // unwritten
+    q.out_offsets = q.in_offsets;
+    return q;
+}
+
+int enet_control_frame_open_batch(const enet_records* r, const uint32_t* session, uint32_t sessions,
+                                  const uint32_t* mid, const uint8_t* sender_ids, uint8_t* chunk_ids_out,
+                                  uint8_t* peer_ids_out, uint8_t* info, uint8_t* status, void* stream) {
+    if (!r) return fail(ENET_EINVAL, "records descriptor is NULL");
+    if (r->count == 0) return ENET_OK;
+    if (!chunk_ids_out || !info || !status) return fail(ENET_EINVAL, "control_frame_open: NULL chunk_ids_out, info or status");
+    if (!aligned4(sender_ids) || !aligned4(chunk_ids_out) || !aligned4(peer_ids_out) || !aligned4(info))
+        return fail(ENET_EINVAL, "control_frame_open: sender_ids, chunk_ids_out, peer_ids_out or info misaligned");
+    const enet_records q = received_frames(r);
+    if (int e = check_records(&q, true)) return e;
+    enet::ControlFrameParams c{};
+    c.d = duplex_params(&q);
+    c.d.out = nullptr;
+    if (int e = chunk_frame_keys(c.d, session, sessions, mid, "control_frame_open: NULL/misaligned session or mid, or no sessions")) return e;
+    c.sender_ids = sender_ids;
+    c.chunk_ids_out = chunk_ids_out;
+    c.peer_ids_out = peer_ids_out;
+    c.info = info;
+    c.status = status;
+    return hip_status(enet::launch_control_frames(enet::CT_OPEN, c, (hipStream_t)stream), "control_frame_open");
+}
+
+int enet_frame_classify_batch(const enet_records* r, const uint32_t* session, uint32_t sessions, uint8_t* kind,
+                              uint32_t* lists, uint32_t* counts, void* stream) {
+    if (!r) return fail(ENET_EINVAL, "records descriptor is NULL");
+    if (r->count == 0) return ENET_OK;
+    if (!kind || !lists || !counts) return fail(ENET_EINVAL, "frame_classify: NULL kind, lists or counts");
+    if (!aligned4(lists) || !aligned4(counts)) return fail(ENET_EINVAL, "frame_classify: lists or counts misaligned");
+    const enet_records q = received_frames(r);
+    if (int e = check_records(&q, true)) return e;
+    enet::ControlFrameParams c{};
+    c.d = duplex_params(&q);
+    c.d.out = nullptr;
+    if (session) {  // the table's keys; no MAC is computed, so no midstates
+        if (!aligned4(session) || sessions == 0) return fail(ENET_EINVAL, "frame_classify: misaligned session, or no sessions");
+        c.d.session = session;
+        c.d.n_sessions = sessions;
+    }
+    c.kind = kind;
+    c.lists = lists;
+    c.counts = counts;
+    return hip_status(enet::launch_control_frames(enet::CT_CLASSIFY, c, (hipStream_t)stream), "frame_classify");
+}
+
 int enet_pow_search_batch(uint32_t n, const uint8_t* prefixes, const uint64_t* prefix_offsets,
                           const uint8_t* difficulty, int schedule, uint64_t max_attempts,
                           uint64_t* nonces, uint64_t* attempts, uint8_t* found, void* stream) {

@@ -178,6 +178,34 @@ struct AnnounceFrameParams {
 };
 hipError_t launch_announce_frames(bool open, const AnnounceFrameParams& p, hipStream_t s);
 
+// Request / Acknowledge frames and frame triage (control_frames.hip).  d carries the arenas,
+// offsets, order and the session keys as for the chunk and announce frames (seal: in_off = out_off,
+// d.in unused; open and classify: out_off = in_off, d.out unused).  The id tables, info, lists
+// and counts are 4-byte aligned (checked by the C ABI).
+constexpr uint32_t kControlRecsPerWG = 64;
+enum ControlOp : int { CT_SEAL = 0, CT_OPEN = 1, CT_CLASSIFY = 2 };
+struct ControlFrameParams {
+    DuplexParams d;
+    // seal
+    const uint8_t* kinds;       // [n]: 2 Request, 4 Acknowledge
+    const uint8_t* chunk_ids;   // [n][32]
+    const uint8_t* peer_id;     // [32] the local id
+    const uint8_t* accepted;    // [n], nullable -> 0
+    int accept_zero;            // the wire byte is accepted[i] == 0 instead of != 0
+    const uint8_t* versions;    // [n], nullable -> 4; clamped to 1..4
+    // open
+    const uint8_t* sender_ids;  // [n][32], nullable
+    uint8_t* chunk_ids_out;     // [n][32]
+    uint8_t* peer_ids_out;      // [n][32], nullable
+    uint8_t* info;              // [n][4]: version, type, accepted, sender_match
+    uint8_t* status;            // seal / open: ENET_CT_* of enet_crypto.h
+    // classify
+    uint8_t* kind;              // [n]: ENET_FK_*
+    uint32_t* lists;            // [5][n]
+    uint32_t* counts;           // [5]
+};
+hipError_t launch_control_frames(ControlOp op, const ControlFrameParams& p, hipStream_t s);
+
 // waves per searching workgroup: enough that a grid of n jobs holds ~4 waves per SIMD (1024
 // SIMDs), at most 16 (1024 threads), never more lanes than attempts
 inline uint32_t pow_search_waves(uint32_t n, uint64_t max_attempts) {

@@ -358,6 +358,92 @@ ENET_API int enet_announce_frame_open_batch(const enet_records* r, const uint32_
                                             const uint32_t* mid, const uint8_t* peer_ids, uint32_t difficulty,
                                             uint32_t* info, uint8_t* status, void* stream);
 
+/* ---- Request / Acknowledge frames and receive-side frame triage
+ *      (additive: enet_abi_version() is unchanged, no existing call changes).
+ * A chunk transfer opens with a `Request` (Node::request_chunk, src/core/Node.cpp:1748-1756;
+ * send_chunk_request_direct, :532-550) and closes with an `Acknowledge` (handle_chunk, :2305-2317;
+ * send_negative_ack, :930-949).  With v = clamp_version(version) (src/protocol/Message.cpp:17-25;
+ * encode, :236-252; payloads, :134-143 and :160-170; encode_signed, :305-311; SessionManager::send,
+ * src/network/SessionManager.cpp:362-387):
+ *   Request      m = v || 0x02 || chunk_id(32) || requester(32)                |m| = 66
+ *   Acknowledge  m = v || 0x04 || accepted(1) || chunk_id(32) || peer_id(32)   |m| = 67
+ *   frame = nonce(12) || BE32(|m| + 32) || ChaCha20_{Ks,nonce,0}(m || HMAC_Ks(m))   114 / 115 bytes
+ * Session keys for all three calls: as in enet_chunk_frame_*_batch (session != NULL: r->keys is the
+ * [sessions][32] table and mid its enet_hmac_midstates; session == NULL: per-record keys through
+ * r->keys / r->key_stride, the HMAC pads computed per record).  count, order and the hints keep
+ * their enet_records meaning.  All arrays are device pointers, [n] entries indexed by record; the
+ * 32-byte id tables, info, lists and counts are 4-byte aligned.
+ * seal: r->in / r->in_offsets are ignored; r->nonces = the frame nonces; out_i = frame_i and
+ *       out_offsets must give |out_i| = 114 (Request) or 115 (Acknowledge).  kinds [n] uint8 =
+ *       ENET_CTL_REQUEST / ENET_CTL_ACK; chunk_ids [n][32]; peer_id [32] = the local id (the
+ *       requester of a Request, the peer_id of an Acknowledge); versions [n] uint8, NULL = 4,
+ *       clamped to 1..4; accepted [n] uint8 (nullable, Acknowledge records only): NULL = 0
+ *       (send_negative_ack); accept_zero == 0: the wire byte is accepted[i] != 0; accept_zero != 0:
+ *       it is accepted[i] == 0, so the status[] of enet_chunk_frame_open_batch can be passed as it
+ *       is (handle_chunk's accepted = plaintext.has_value(), Node.cpp:2305-2317).  status [n]:
+ *         0 ENET_CT_OK
+ *         1 ENET_CT_FRAME   the output length does not fit, or the session index is outside the table
+ *         2 ENET_CT_HEADER  the kind is not 2 or 4 (checked first: no kind, no length to fit)
+ *       On a non-zero status the record's whole output slot is zero.  One launch, no allocation, no
+ *       synchronisation; m never exists in device memory.
+ * open: in_i = a received frame (the nonce is read from it; r->nonces may be NULL); r->out /
+ *       r->out_offsets are ignored and may be NULL.  Outputs are SoA: chunk_ids_out [n][32],
+ *       peer_ids_out [n][32] (nullable; the requester / peer_id field), info [n][4] uint8 = {v, type,
+ *       accepted, sender_match}: accepted = the wire byte != 0 (Message.cpp:160-170), 0 for a
+ *       Request; sender_match = 1 when sender_ids ([n][32], nullable: the peer of each frame's
+ *       session) is given and equals the message's requester / peer_id, else 0 -- reported, not
+ *       enforced, because the reference acts on the transport's sender and never reads the
+ *       payload's id (handle_request, Node.cpp:2255-2284; handle_acknowledge, :2320-2330).
+ *       status [n] = the first failed check:
+ *         0 ENET_CT_OK
+ *         1 ENET_CT_FRAME   what gives enet_wire_open_batch ok = 0: frame < 48 bytes, length field
+ *                           != body length, HMAC mismatch, session index outside the table
+ *         2 ENET_CT_HEADER  version outside 1..4, type not 2 or 4, or |m| != 66 (Request) / 67
+ *                           (Acknowledge)
+ *       On a non-zero status the record's chunk id, peer id and info are zero.  Records `order` does
+ *       not name are untouched.  One deliberate difference, as for Chunk and Announce frames:
+ *       decode accepts trailing bytes (remaining < needed is its only check, Message.cpp:134-143,
+ *       160-170); this call reports ENET_CT_HEADER and the caller falls back to
+ *       enet_wire_open_batch_sessions.  One launch; every frame byte is read from HBM once.
+ * classify: in_i = a received frame of unknown type; no mid is needed and nothing is authenticated:
+ *       one ChaCha20 block (counter 0), the 16 header bytes and the first 2 body bytes per frame.
+ *       kind [n] uint8:
+ *         0 ENET_FK_BAD       L < 48, BE32(frame[12..16)) != L - 16 (SessionManager.cpp:770-796), or
+ *                             the session index is outside the table: what every open call rejects
+ *                             as FRAME without looking at the body
+ *         1 ENET_FK_ANNOUNCE  v in 1..4, type 1, |m| = L - 48 >= 82 + (v >= 3 ? 8 : 0) (Message.cpp:75-121)
+ *         2 ENET_FK_REQUEST   v in 1..4, type 2, |m| == 66
+ *         3 ENET_FK_CHUNK     v in 1..4, type 3, |m| >= 42 (Message.cpp:144-159)
+ *         4 ENET_FK_ACK       v in 1..4, type 4, |m| == 67
+ *         5 ENET_FK_OTHER     everything else (types 5 and 6, other versions, |m| < 2, a length that
+ *                             does not fit its class): for enet_wire_open_batch_sessions
+ *       lists [5][n] uint32 (n = r->count) and counts [5] uint32: row k - 1 holds the indices of the
+ *       frames of kind k, each index exactly once, BAD frames in no row; ascending inside each
+ *       256-record block of the batch, the blocks in any order.  The call zeroes counts on the
+ *       stream itself.  The host reads counts (20 bytes) and passes lists + (k - 1) * n as `order`
+ *       and counts[k - 1] as `count` to the matching open on the same stream.
+ *       PROPERTY: a frame for which enet_announce_frame_open_batch, enet_chunk_frame_open_batch or
+ *       enet_control_frame_open_batch would return status 0 is always classified into that call's
+ *       class -- every class test is implied by the open's own header check, so triage never costs
+ *       a frame its fast path.  The reverse does not hold: a forged frame may land in a class and
+ *       then get FRAME or HEADER from the open.
+ * ENET_EINVAL, with nothing launched: NULL r, kinds, chunk_ids, peer_id, status, chunk_ids_out,
+ * info, kind, lists or counts; misaligned id tables, info, lists or counts; the session / mid rules
+ * of the chunk frames.  count == 0 is a no-op whatever else is passed. */
+enum { ENET_CTL_REQUEST = 2, ENET_CTL_ACK = 4 };
+enum { ENET_CT_OK = 0, ENET_CT_FRAME = 1, ENET_CT_HEADER = 2 };
+enum { ENET_FK_BAD = 0, ENET_FK_ANNOUNCE = 1, ENET_FK_REQUEST = 2, ENET_FK_CHUNK = 3, ENET_FK_ACK = 4,
+       ENET_FK_OTHER = 5 };
+ENET_API int enet_control_frame_seal_batch(const enet_records* r, const uint32_t* session, uint32_t sessions,
+                                           const uint32_t* mid, const uint8_t* kinds, const uint8_t* chunk_ids,
+                                           const uint8_t* peer_id, const uint8_t* accepted, int accept_zero,
+                                           const uint8_t* versions, uint8_t* status, void* stream);
+ENET_API int enet_control_frame_open_batch(const enet_records* r, const uint32_t* session, uint32_t sessions,
+                                           const uint32_t* mid, const uint8_t* sender_ids, uint8_t* chunk_ids_out,
+                                           uint8_t* peer_ids_out, uint8_t* info, uint8_t* status, void* stream);
+ENET_API int enet_frame_classify_batch(const enet_records* r, const uint32_t* session, uint32_t sessions,
+                                       uint8_t* kind, uint32_t* lists, uint32_t* counts, void* stream);
+
 /* ---- session key derivation
  * network::KeyManager::derive_key (src/network/KeyManager.cpp:74-92) for n sessions:
  * keys_out[i] = HMAC-SHA256(secrets[i], BE64(counters[i]) || BE64(ticks[i])), ticks = the

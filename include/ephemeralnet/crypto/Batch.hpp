@@ -258,6 +258,60 @@ ENET_CXX_API std::vector<OpenedAnnounce> announce_frames_open(
     std::span<const std::array<std::uint8_t, 32>> session_table, std::span<const std::uint32_t> session,
     std::span<const std::span<const std::uint8_t>> frames, std::span<const PeerId> peers, std::uint8_t difficulty);
 
+// Request / Acknowledge frames and frame triage (enet_control_frame_*_batch,
+// enet_frame_classify_batch): the messages that open and close a chunk transfer, batched.
+// control_frames_seal is Node::request_chunk's and handle_chunk's / send_negative_ack's crypto
+// (Node.cpp:1748-1756, 532-550, 2305-2317, 930-949) for many peers at once: frame i = the wire
+// frame, under session_table[session[i]] and nonces[i], of the signed message encode writes
+// (Message.cpp:236-252; the version clamped to 1..4) -- version || 0x02 || chunk_id || local_id
+// for a Request (114 bytes), version || 0x04 || accepted || chunk_id || local_id for an
+// Acknowledge (115 bytes).  A record whose kind is neither comes back with status Header and an
+// empty frame.
+// control_frames_open is the receive side (decode_signed): status = the first failed check --
+// Frame: what the general open rejects; Header: a version outside 1..4, another type, or a
+// message that is not exactly 66 / 67 bytes (decode would accept trailing bytes; encode never
+// writes them).  sender_match reports whether the message's requester / peer_id equals
+// senders[i] (senders may be left empty: false); it is not enforced -- the reference acts on the
+// transport's sender (handle_request, Node.cpp:2255-2284; handle_acknowledge, :2320-2330).  A
+// failed frame comes back with zeroed fields.
+// classify_frames is the triage of a mixed receive batch (receive loop,
+// SessionManager.cpp:760-822; handle_transport_message, Node.cpp:2160-2179): one keystream block
+// per frame, nothing authenticated; Bad = what every open rejects without reading the body, Other
+// = for the general open.  A frame a fused open would accept is always given that open's kind.
+// All three throw std::invalid_argument for a size mismatch or a session index outside the table;
+// empty in gives empty out.
+enum class ControlKind : std::uint8_t { Request = 2, Acknowledge = 4 };
+enum class ControlStatus : std::uint8_t { Ok = 0, Frame = 1, Header = 2 };
+enum class FrameKind : std::uint8_t { Bad = 0, Announce = 1, Request = 2, Chunk = 3, Acknowledge = 4, Other = 5 };
+struct ControlFields {
+    ControlKind kind = ControlKind::Request;
+    ChunkId chunk_id{};
+    bool accepted = false;  // Acknowledge only
+    std::uint8_t version = 4;
+};
+struct SealedControls {
+    std::vector<std::vector<std::uint8_t>> frames;
+    std::vector<ControlStatus> status;
+};
+struct OpenedControl {
+    ControlStatus status = ControlStatus::Frame;
+    std::uint8_t version = 0;
+    std::uint8_t type = 0;  // 2 Request, 4 Acknowledge
+    bool accepted = false;
+    ChunkId chunk_id{};
+    PeerId peer_id{};
+    bool sender_match = false;
+};
+ENET_CXX_API SealedControls control_frames_seal(
+    std::span<const std::array<std::uint8_t, 32>> session_table, std::span<const std::uint32_t> session,
+    std::span<const Nonce> nonces, std::span<const ControlFields> controls, const PeerId& local_id);
+ENET_CXX_API std::vector<OpenedControl> control_frames_open(
+    std::span<const std::array<std::uint8_t, 32>> session_table, std::span<const std::uint32_t> session,
+    std::span<const std::span<const std::uint8_t>> frames, std::span<const PeerId> senders = {});
+ENET_CXX_API std::vector<FrameKind> classify_frames(
+    std::span<const std::array<std::uint8_t, 32>> session_table, std::span<const std::uint32_t> session,
+    std::span<const std::span<const std::uint8_t>> frames);
+
 // Cross-session frame queues.  SessionManager runs one detached reader
 // thread per session (SessionManager.cpp:332-333, receive_loop :703-854) and sends from whatever
 // thread calls Node::send_secure (:337-388), one ChaCha20 + HMAC per frame on that thread.  Here
