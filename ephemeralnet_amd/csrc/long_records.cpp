@@ -137,15 +137,14 @@ int seg_begin(int mode, const enet_records* r, RecParams& p, uint64_t long_min, 
     q.entry_cap = (uint32_t)lay.ecap;
     q.tile_cap = (uint32_t)lay.tcap;
     q.long_min = long_min;
-    const uint32_t plan_blocks = (uint32_t)std::min<uint64_t>((n + 255) / 256, 1024);
-    const uint32_t tile_blocks = (uint32_t)std::min<uint64_t>(lay.tcap, 4096);
+    const SegGrid grid = seg_grid(n, lay);  // capped: both kernels stride past the caps
     p.skip = q.claimed;
     // per-lane path: the staged paths assume every record is theirs.  It also makes the record
     // engine ONE launch over positions 0 .. n-1 (rec_base == 0), which is what lets the plan
     // kernel and records_body agree on claimed[position]
     p.uniform_len = 0;
     g_seg_batches.fetch_add(1, std::memory_order_relaxed);
-    return hip_status(launch_seg(q, plan_blocks, tile_blocks, st), "sequence-parallel launch");
+    return hip_status(launch_seg(q, grid.plan_blocks, grid.tile_blocks, st), "sequence-parallel launch");
 }
 
 }  // namespace

@@ -94,6 +94,20 @@ inline SegLayout seg_layout(uint32_t count, uint32_t max_len_hint, uint64_t tota
     return l;
 }
 
+// Launch sizes of the plan + tiles path (long_records.cpp seg_begin).  Both kernels walk their work
+// in grid strides past these caps: the plan kernel (256 positions per workgroup) beyond
+// 256 * kSegPlanBlocksMax = 262 144 positions, the tile kernel (one tile per workgroup and trip)
+// beyond kSegTileBlocksMax tiles of capacity.
+constexpr uint32_t kSegPlanThreads = 256;
+constexpr uint32_t kSegPlanBlocksMax = 1024;
+constexpr uint32_t kSegTileBlocksMax = 4096;
+struct SegGrid { uint32_t plan_blocks, tile_blocks; };
+inline SegGrid seg_grid(uint32_t count, const SegLayout& l) {
+    const uint64_t pb = ((uint64_t)count + kSegPlanThreads - 1) / kSegPlanThreads;
+    return {(uint32_t)(pb < kSegPlanBlocksMax ? pb : kSegPlanBlocksMax),
+            (uint32_t)(l.tcap < kSegTileBlocksMax ? l.tcap : kSegTileBlocksMax)};
+}
+
 // Which claim byte the record at position pos of the launch (record index rec) owns: the plan
 // kernel writes it and records_body reads it through this one rule.  By position: pos < count
 // always, while rec is whatever the caller's order names (one length class of a larger batch).

@@ -271,11 +271,20 @@ int main() {
             std::string id, p; in >> id >> p;
             ChunkId cid; auto ib = unhex(id);
             std::copy(ib.begin(), ib.end(), cid.begin());
-            auto key = crypto::CryptoManager::generate_key();
             ChunkData pt = unhex(p);
-            auto ct = crypto::CryptoManager::encrypt_with_key(key, cid, pt);
-            auto back = crypto::CryptoManager::decrypt_with_key(key, cid, ct.data, ct.nonce);
-            std::cout << ((back && *back == pt && (pt.empty() || ct.data != pt)) ? "1" : "0") << "\n";
+            // The key and nonce are random: a 1-byte ciphertext equals its plaintext under one key
+            // in 256 (this case failed the suite that way once), so "the ciphertext differs" is
+            // asked of up to eight fresh keys (2^-64 for the golden 1-byte case), every one of
+            // which must round-trip.
+            bool good = true, differs = false;
+            for (int k = 0; k < 8 && good && !differs; ++k) {
+                auto key = crypto::CryptoManager::generate_key();
+                auto ct = crypto::CryptoManager::encrypt_with_key(key, cid, pt);
+                auto back = crypto::CryptoManager::decrypt_with_key(key, cid, ct.data, ct.nonce);
+                good = back && *back == pt;
+                differs = pt.empty() || ct.data != pt;
+            }
+            std::cout << (good && differs ? "1" : "0") << "\n";
         } else if (op == "frame_seal") {
             std::string k, n, m; in >> k >> n >> m;
             std::array<uint8_t, 32> key{}; crypto::Nonce nonce;

@@ -1,5 +1,5 @@
 // The routing rule for long records (csrc/long_route.hpp choose_long_route) and the scratch
-// layout of the plan + tiles path (seg_layout, seg_claim_slot) against tables worked out by hand
+// layout and launch sizes of the plan + tiles path (seg_layout, seg_claim_slot, seg_grid) against tables worked out by hand
 // from the rules: host C++ only, exit status 0 when every row agrees.
 #include <cstdint>
 #include <cstdio>
@@ -71,6 +71,21 @@ int layout_rows() {
         // the claim bytes end exactly on a 256-byte line (8 896 + 320 = 9 216), and one past it
         {106, 320, 200000, 613552, 65536, 10, 20, 8896, 9216, 9856, 0xFFFFFEC0u},
         {107, 321, 200000, 613552, 65536, 10, 20, 8896, 9472, 10112, 1},
+        // the shapes of tests/test_gpu_tile_limits.py (their launch sizes: grid_rows below).
+        // 4 300 records under long_min 0, 4 293 of them 0 .. 4 095 bytes and seven of 65 536 ..
+        // 1 MiB: S = 4 386 479, S / 64 KiB = 66, ecap = n, tcap = 66 + 4 300 + 1; the entries alone
+        // (4 300 E = 3 715 200 bytes) are past the 256 KiB floor of the plan scratch
+        {108, 4300, 1048576, 4386479, 0, 4300, 4367, 3715456, 3719936, 3859680, 0},
+        // 257 MiB + 17 and 300 KiB under the automatic threshold: S / 256 KiB + 1 = 1 030 > n,
+        // S / 64 KiB = 4 116, tcap = 4 116 + 2 + 1; 133 856 bytes, inside the floor
+        {109, 2, 269484049, 269791249, 262144, 2, 4119, 1984, 2048, 133856, 0},
+        // 262 444 records of 1 .. 3 bytes but three (262 244, 65 537, 307 200), threshold 64 KiB:
+        // S / 64 KiB = 17, ecap 18, tcap 36; the claim bytes are [15 808, 278 252), those of the
+        // positions from 262 144 on (the plan kernel's second trip) [277 952, 278 252)
+        {110, 262444, 307200, 1159863, 65536, 18, 36, 15808, 278272, 279424, 0},
+        // the first 320 records of row 108's batch: its partials start at 277 248, so tiles 22 .. 31
+        // of it lie on row 110's second-trip claim bytes
+        {111, 320, 65536, 237664, 0, 320, 324, 276736, 277248, 287616, 0},
     };
     int bad = 0;
     for (const LayoutRow& w : rows) {
@@ -102,6 +117,46 @@ int layout_rows() {
             std::printf("        a claim byte lies outside [%llu, %llu)\n", (unsigned long long)l.o_cl,
                         (unsigned long long)(l.o_cl + w.count));
         bad += !(ok && inside);
+    }
+    return bad;
+}
+
+// seg_grid: the launch sizes of the plan + tiles path, capped at kSegPlanBlocksMax workgroups of
+// 256 positions and kSegTileBlocksMax tile workgroups; the kernels stride past the caps.
+struct GridRow {
+    int id;
+    uint32_t count;
+    uint64_t M, S, long_min;
+    uint32_t plan_blocks, tile_blocks;
+};
+
+int grid_rows() {
+    static_assert(enet::kSegPlanBlocksMax == 1024 && enet::kSegTileBlocksMax == 4096 && enet::kSegPlanThreads == 256,
+                  "the caps the rows below were worked out for");
+    const GridRow rows[] = {
+        // under both caps: ceil(512 / 256) = 2 plan workgroups, tcap = 20 tile workgroups (row 101)
+        {201, 512, 200000, 613552, 65536, 2, 20},
+        {202, 1, 0, 0, 0, 1, 2},
+        // the last n that fits one plan trip, and the first that does not
+        {203, 262144, 3, 786432, 65536, 1024, 26},
+        {204, 262145, 3, 786435, 65536, 1024, 26},
+        // layout rows 108 .. 110: 4 367 and 4 119 tiles of capacity on 4 096 workgroups (a second
+        // trip of the tile loop); 262 444 positions on 1 024 plan workgroups (a second trip there)
+        {205, 4300, 1048576, 4386479, 0, 17, 4096},
+        {206, 2, 269484049, 269791249, 262144, 1, 4096},
+        {207, 262444, 307200, 1159863, 65536, 1024, 36},
+        // exactly at the tile cap: tcap = 4 093 + 2 + 1 = 4 096 (S = 4 093 * 64 KiB)
+        {208, 2, 268238848, 268238848 + 1, 262144, 1, 4096},
+    };
+    int bad = 0;
+    for (const GridRow& w : rows) {
+        const enet::SegLayout l = enet::seg_layout(w.count, (uint32_t)w.M, w.S, w.long_min);
+        const enet::SegGrid g = enet::seg_grid(w.count, l);
+        const bool ok = g.plan_blocks == w.plan_blocks && g.tile_blocks == w.tile_blocks;
+        std::printf("grid %d: plan %u tiles %u (tcap %llu)%s\n", w.id, g.plan_blocks, g.tile_blocks,
+                    (unsigned long long)l.tcap, ok ? "" : "   <-- MISMATCH");
+        if (!ok) std::printf("        wanted plan %u tiles %u\n", w.plan_blocks, w.tile_blocks);
+        bad += !ok;
     }
     return bad;
 }
@@ -167,5 +222,6 @@ int main() {
         }
     }
     bad += layout_rows();
+    bad += grid_rows();
     return bad ? 1 : 0;
 }

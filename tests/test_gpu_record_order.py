@@ -52,18 +52,22 @@ def enet():
 
 
 @functools.lru_cache(maxsize=None)
-def batch_data(lens, seed, base, ctr_kind):
+def batch_data(lens, seed, base, ctr_kind, aad_lens=AAD_LENS, shared_key=False, refs=None, xor=True):
     """A batch of len(lens) records starting at `base` in its arena, and the oracle's seal
-    (AAD lengths cycling through 0, 1, 16, 17), and ChaCha20 (per-record start counters) of every
-    record, laid out like the arena.  Computed once per batch; nothing mutates it."""
+    (AAD lengths cycling through aad_lens: 0, 1, 16, 17), and ChaCha20 (per-record start counters)
+    of every record, laid out like the arena.  Computed once per batch; nothing mutates it.
+    shared_key: one key for the batch (key_stride 0).  refs: the records to compute the oracle's
+    values for (a tuple; None = all: the others' ranges of ct / xo / tags stay zero, for batches too
+    large to check in full).  xor = False leaves xo zero (AEAD-only batches of many MiB).
+    batch_data.__wrapped__ builds a batch without keeping it."""
     n = len(lens)
     offs = (base + np.concatenate([[0], np.cumsum(lens)])).astype(np.int64)
     size = max(int(offs[-1]), 1)
     pt = np.zeros(size, dtype=np.uint8)
     pt[base:int(offs[-1])] = np.frombuffer(splitmix_bytes(seed, int(offs[-1]) - base), dtype=np.uint8)
-    keys = splitmix_bytes(seed + 1, 32 * n)
+    keys = splitmix_bytes(seed + 1, 32 * (1 if shared_key else n))
     nonces = splitmix_bytes(seed + 2, 12 * n)
-    aoff = np.concatenate([[0], np.cumsum([AAD_LENS[i % 4] for i in range(n)])]).astype(np.int64)
+    aoff = np.concatenate([[0], np.cumsum([aad_lens[i % len(aad_lens)] for i in range(n)])]).astype(np.int64)
     aad = splitmix_bytes(seed + 3, int(aoff[-1]))
     if ctr_kind == "mod7":  # the u32 wrap falls before one of the first seven blocks, or nowhere
         ctr = np.array([(-(i % 7)) & 0xFFFFFFFF for i in range(n)], dtype=np.uint32)
@@ -71,18 +75,20 @@ def batch_data(lens, seed, base, ctr_kind):
         ctr = np.array([0xFFFFFFFF - (i * 977) % 4096 for i in range(n)], dtype=np.uint32)
     ct, xo = np.zeros_like(pt), np.zeros_like(pt)
     tags = np.zeros(16 * n, dtype=np.uint8)
-    for i in range(n):
-        k, nn = keys[32 * i:32 * i + 32], nonces[12 * i:12 * i + 12]
+    for i in (range(n) if refs is None else refs):
+        k = keys[:32] if shared_key else keys[32 * i:32 * i + 32]
+        nn = nonces[12 * i:12 * i + 12]
         m = pt[offs[i]:offs[i + 1]].tobytes()
         c, t = oracle.aead_seal(k, nn, m, aad[aoff[i]:aoff[i + 1]])
         ct[offs[i]:offs[i + 1]] = np.frombuffer(c, dtype=np.uint8)
         tags[16 * i:16 * i + 16] = np.frombuffer(t, dtype=np.uint8)
-        xo[offs[i]:offs[i + 1]] = np.frombuffer(oracle.chacha20_xor(k, nn, m, int(ctr[i])), dtype=np.uint8)
+        if xor:
+            xo[offs[i]:offs[i + 1]] = np.frombuffer(oracle.chacha20_xor(k, nn, m, int(ctr[i])), dtype=np.uint8)
     for a in (offs, pt, aoff, ctr, ct, xo, tags):
         a.setflags(write=False)
     as_u8 = lambda b: np.frombuffer(b or b"\0", dtype=np.uint8)
     return SimpleNamespace(n=n, lens=lens, base=base, offs=offs, size=size, pt=pt, keys=as_u8(keys),
-                           nonces=as_u8(nonces), aad=as_u8(aad), aoff=aoff, ctr=ctr, ct=ct, xo=xo, tags=tags)
+                           key_stride=0 if shared_key else 32, refs=refs, nonces=as_u8(nonces), aad=as_u8(aad), aoff=aoff, ctr=ctr, ct=ct, xo=xo, tags=tags)
 
 
 class Guarded:
@@ -117,22 +123,25 @@ def same(got, want, bounds, what):
                              f"want {int(want[d[0]]):#x}; {d.size} bytes differ")
 
 
-def run_ops(enet, d, order, *, tag_victim, ct_victim, hints=None, want_route=None, want_seg=None,
+def run_ops(enet, d, order, *, tag_victim, ct_victim, aad_victim=None, hints=None, want_route=None, want_seg=None,
             ops=("xor", "seal", "open", "tamper"), tag=""):
     """The cipher calls over the records `order` names (None: all, in batch order) of batch d, each
     into prefilled outputs, each checked as the module text says.  tag_victim: a named record whose
-    tag gets one bit flipped, ct_victim = (named record, byte of it to flip) for the tampered open.
+    tag gets one bit flipped, ct_victim = (named record, byte of it to flip), aad_victim: a third
+    named record whose first AAD byte is flipped, for the tampered open (None: no such flip).
     want_route / want_seg: what every call must add to record_route_counts() / seg_batches().
     Returns the outputs (host arrays) by name."""
     import torch
+    assert d.refs is None, "run_ops compares every record"
     named = list(range(d.n)) if order is None else [int(i) for i in order]
-    assert len(set(named)) == len(named) and tag_victim in named and ct_victim[0] in named
+    victims = [v for v in (tag_victim, ct_victim and ct_victim[0], aad_victim) if v is not None]
+    assert len(set(named)) == len(named) and set(victims) <= set(named) and len(set(victims)) == len(victims)
     if hints is None:  # of the named records
         hints = dict(total_bytes_hint=sum(d.lens[i] for i in named), max_len_hint=max(d.lens[i] for i in named))
     dev = lambda a: torch.from_numpy(np.array(a)).cuda()
     toffs, keys, nonces, aad, aoff = dev(d.offs), dev(d.keys), dev(d.nonces), dev(d.aad), dev(d.aoff)
     tord = None if order is None else torch.tensor(named, dtype=torch.int32, device="cuda")
-    batch = lambda arena: enet.Batch(arena, toffs, keys, nonces, order=tord,
+    batch = lambda arena: enet.Batch(arena, toffs, keys, nonces, key_stride=d.key_stride, order=tord,
                                      count=None if order is None else len(named), **hints)
     b16, b1 = 16 * np.arange(d.n + 1), np.arange(d.n + 1)
 
@@ -167,15 +176,21 @@ def run_ops(enet, d, order, *, tag_victim, ct_victim, hints=None, want_route=Non
         same(res["open_ok"], only_named(ones, b1, named), b1, f"{tag} open verdicts")
         same(res["open"], only_named(d.pt, d.offs, named), d.offs, f"{tag} open plaintext")
     if "tamper" in ops:
-        bad_ct, bad_tags = ct_in.clone(), dev(d.tags)
-        bad_tags[16 * tag_victim + 5] ^= 0x08
-        v, pos = ct_victim
-        assert 0 <= pos < d.lens[v] and v != tag_victim
-        bad_ct[int(d.offs[v]) + pos] ^= 0x20
+        assert victims
+        bad_ct, bad_tags, bad_aad = ct_in.clone(), dev(d.tags), aad.clone()
+        if tag_victim is not None:
+            bad_tags[16 * tag_victim + 5] ^= 0x08
+        if ct_victim is not None:
+            v, pos = ct_victim
+            assert 0 <= pos < d.lens[v]
+            bad_ct[int(d.offs[v]) + pos] ^= 0x20
+        if aad_victim is not None:
+            assert d.aoff[aad_victim + 1] > d.aoff[aad_victim]
+            bad_aad[int(d.aoff[aad_victim])] ^= 0x01
         out, ok = Guarded(d.size), Guarded(d.n)
-        launch(enet.aead_open, batch(bad_ct), out.view, bad_tags, ok.view, aad, aoff)
+        launch(enet.aead_open, batch(bad_ct), out.view, bad_tags, ok.view, bad_aad, aoff)
         want_pt, want_ok = d.pt.copy(), ones.copy()
-        for f in (tag_victim, v):  # no verdict, no plaintext
+        for f in victims:  # no verdict, no plaintext
             want_pt[d.offs[f]:d.offs[f + 1]] = 0
             want_ok[f] = 0
         res["tamper"], res["tamper_ok"] = out.host(), ok.host()

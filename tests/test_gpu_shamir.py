@@ -10,6 +10,7 @@ import hashlib
 import json
 import os
 import subprocess
+import time
 
 import numpy as np
 import pytest
@@ -200,6 +201,35 @@ def test_split_then_combine_on_device(enet, t, sc):
     ok = torch.zeros(n, dtype=torch.uint8, device="cuda")
     enet.shamir_combine(indices, values, t, out, ok)
     assert int(ok.sum()) == n and torch.equal(out, secrets)
+
+
+def test_split_and_combine_past_the_block_cap(enet):
+    """n = 2^21 + 300 records of 2-of-2: 8 n words on workgroups of 256 threads would be 65 546
+    workgroups, over kShamirMaxBlocks = 65 536 (shamir.hip), so the records from 2 097 152 on are
+    reached only by the kernels' grid-stride step.  Every share against gf256_ref.split; combine
+    from the shares in the order (2, 1) gives every secret back -- gf256_ref.combine agrees on the
+    records at both ends -- except record n - 7, whose two indices are equal: ok = 0, 32 zero bytes."""
+    t0 = time.time()
+    n, t, sc = (1 << 21) + 300, 2, 2
+    assert -(-8 * n // 256) == 65546 > 65536 and 65536 * 256 // 8 == 2097152 < n - 7
+    secrets = splitmix_array(61000, n * 32).reshape(n, 32)
+    coeffs = splitmix_array(62000, n * 32).reshape(n, 1, 32)
+    want = G.split(secrets, coeffs, sc)
+    got = run_split(enet, secrets, coeffs, t, sc)
+    assert np.array_equal(got, want), np.argwhere(got != want)[:3].tolist()
+    idx = np.tile(np.array([2, 1], np.uint8), (n, 1))
+    val = np.ascontiguousarray(want[:, ::-1, :])
+    dup = n - 7
+    idx[dup] = (2, 2)
+    ends = np.r_[0:4, n - 12:n]
+    ref_secret, ref_ok = G.combine(idx[ends], val[ends])
+    out, ok = run_combine(enet, idx, val)
+    assert np.array_equal(out[ends], ref_secret) and np.array_equal(ok[ends], ref_ok)
+    assert np.flatnonzero(ok != 1).tolist() == [dup] and ok[dup] == 0
+    expect = secrets.copy()
+    expect[dup] = 0
+    assert np.array_equal(out, expect), np.argwhere(out != expect)[:3].tolist()
+    print(f"\n[shamir] {n} records past the block cap: {time.time() - t0:.1f} s")
 
 
 def chunk_case(n, L, seed):
